@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: chunks/sec of the MVPNet lifting + PointNet++ hot path, fwd+bwd.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; every side measurement and check (below, and the
+`--extras` / `--no-cpu-baseline` / `--train-only` choices among them) runs only with `--full`.  `--dump-outputs DIR` writes what the
+last timed step returned (loss, logits) as float32 .npy files.  The inputs are seeded and the optimizer runs at a learning rate of 0 (the
+weights stay the seeded ones), so two runs, or two builds, can be compared output for output.
 
 N > 1 works either way: under an external `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (WORLD_SIZE set:
 this process IS one rank), or as a plain `python bench.py --gpus N` -- the script then re-executes itself under
@@ -17,7 +22,7 @@ Per GPU: B=32 chunks of 8192 points with 3 views of 160x120 (yaml TRAIN.BATCH_SI
 The frozen 2D CNN (UNetResNet34, out of scope; torchvision is absent) is replaced by a supplied
 64-channel feature map, exactly as the reference's training consumes it (net_2d is frozen).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full, among others, two extra objects:
   roofline     -- the lifting kernels (un-project + pixel k-NN + gather): algorithmic bytes
                   (13 287 936 B/chunk = SURVEY.md sec.8d with the uint16 depth fed here) / their device time measured with HIP
                   events on the launch stream, against the 8 TB/s HBM3E peak;
@@ -105,6 +110,24 @@ class TimedLifting:
 
     def mean_ms(self):
         return float(np.mean([s.elapsed_time(e) for s, e in self.pairs])) if self.pairs else float('nan')
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6 - (1 << 16)   # --dump-outputs: 64 MB in all, .npy headers and the loss included
+
+
+def dump_outputs(path, loss, preds):
+    """--dump-outputs: what the caller of the timed step receives from its last call -- the loss and the model's output tensors
+    (seg_logit, (B, classes, N)) -- as path/<name>.npy in float32.  Beyond DUMP_MAX_BYTES only the leading chunks of the batch are
+    written, the same ones in every run."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss.npy'), loss.detach().float().cpu().numpy())
+    room = DUMP_MAX_BYTES
+    for name, t in preds.items():
+        if torch.is_tensor(t):
+            per_chunk = 4 * t[0].numel()
+            t = t.detach()[:room // per_chunk]
+            room -= per_chunk * t.size(0)
+            np.save(os.path.join(path, name + '.npy'), t.float().cpu().numpy())
 
 
 TRAFFIC_FILES = ('r06_step_traffic.json', 'r05_step_traffic.json', 'r04_step_traffic.json', 'r03_step_traffic.json')  # the newest committed PMC table of the step
@@ -367,28 +390,28 @@ def collective_info(dev=None):
     return info
 
 
-SETTLE_BLOCK, SETTLE_MAX_BLOCKS, SETTLE_TOL = 10, 12, 0.01
+SETTLE_BLOCK, SETTLE_BLOCKS = 10, 12
 
 
-SETTLE_BLOCKS_MULTI = 4   # N > 1: a FIXED number of blocks (every step holds a gradient all-reduce: all ranks must run the same count)
+SETTLE_BLOCKS_MULTI = 4   # N > 1: fewer blocks (every step holds a gradient all-reduce: all ranks must run the same count)
 
 
-def settle(step, fixed_blocks=0):
-    """Part of the set-up, before the contract's warm-up steps: run the step in blocks of 10 until a block is within 1 % of the one before
-    it (at most 120 steps, ~1 s).  On a fresh box the first few dozen steps after the model is built are 2-3 % slower than the steady
-    state -- clocks ramping up from idle, the caching allocator's pools of the three streams reaching their final shape, first use of
-    every kernel's code object (BENCH_r04: 7.448 / 7.299 / 7.252 ms for three identical 20-step regions) -- and the contract's 5 warm-up
-    steps (37 ms) end before that does.  The W warm-up and K timed steps behind this are untouched.  -> (blocks run, ms per step of each)."""
+def settle(step, blocks):
+    """Part of the set-up, before the contract's warm-up steps: `blocks` blocks of 10 steps (one rank: 120 steps, ~1 s).  On a fresh box
+    the first few dozen steps after the model is built are 2-3 % slower than the steady state -- clocks ramping up from idle, the caching
+    allocator's pools of the three streams reaching their final shape, first use of every kernel's code object (BENCH_r04: 7.448 / 7.299 /
+    7.252 ms for three identical 20-step regions) -- and the contract's 5 warm-up steps (37 ms) end before that does.  The count is fixed,
+    not chosen by the timings, so that every run with the same arguments draws the same dropout seeds (one per step from torch's seeded
+    CPU generator) up to its last timed step (--dump-outputs).  The W warm-up and K timed steps behind this are untouched.  -> ms per step
+    of each block."""
     hist = []
-    for _ in range(fixed_blocks or SETTLE_MAX_BLOCKS):
+    for _ in range(blocks):
         torch.cuda.synchronize()
         t = time.perf_counter()
         for _ in range(SETTLE_BLOCK):
             step()
         torch.cuda.synchronize()
         hist.append((time.perf_counter() - t) / SETTLE_BLOCK * 1e3)
-        if not fixed_blocks and len(hist) >= 3 and abs(hist[-1] - hist[-2]) <= SETTLE_TOL * hist[-2] and abs(hist[-2] - hist[-3]) <= SETTLE_TOL * hist[-3]:
-            break
     return [round(h, 3) for h in hist]
 
 
@@ -514,9 +537,10 @@ def peer_run(args):
             p.grad = torch.zeros_like(p)
         sync(weight_sum=torch.tensor(1.0))
 
-    for _ in range(SETTLE_BLOCKS_MULTI * SETTLE_BLOCK):  # the real ranks' set-up steps (bench.settle) and their collective census
+    for _ in range(SETTLE_BLOCKS_MULTI * SETTLE_BLOCK):  # the real ranks' set-up steps (bench.settle) and, with --full, their collective census
         one()
-    collective_info()
+    if args.full:
+        collective_info()
     launch = resolve_launch(args, world)
     use_graph = launch == 'graph'
     if launch == 'auto':  # the real ranks' probe: its eager steps and the MAX all-reduce of their verdicts (a peer has none of its own)
@@ -525,15 +549,15 @@ def peer_run(args):
         flag = torch.zeros(1, dtype=torch.float64)
         torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MAX)
         use_graph = flag.item() > 0
-    n = args.warmup + args.steps + (5 if use_graph else 0)
-    for it in range(n):
-        if it == args.warmup or it == args.warmup + args.steps:  # before the timed steps; (graph: + behind them, before the 5 eager steps)
+    for it in range(args.warmup + args.steps):
+        if it == args.warmup:  # before the timed steps
             torch.distributed.barrier()
         one()
-    if not use_graph:
-        torch.distributed.barrier()
+    torch.distributed.barrier()
     tmax = torch.zeros(1, dtype=torch.float64)
     torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
+    for _ in range(5 if use_graph and args.full else 0):  # the real ranks' eager steps behind a timed replay (--full)
+        one()
     torch.distributed.barrier()
     torch.distributed.destroy_process_group()
 
@@ -562,6 +586,11 @@ def main():
                     'without a result line: with MVP_LIBRARY=mvpnet_amd/libmvp_noop.so (make -C mvpnet_amd/csrc noop) the process issues every '
                     'library call of the step but no kernel of ours runs -- a launch-only peer that loads the host beside ONE timed rank (tools/multi_rank_host.sh)')
     ap.add_argument('--dry', action='store_true', help='launcher / collective plumbing only: gloo on the host, no kernels (CPU test of the N > 1 path)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, every side measurement and check as well: repeats, phase events, '
+                    'lifting roofline, other batch sizes / precisions / configurations, forward-only, scene inference, 2D network, collective '
+                    'census, parity figures, CPU baseline (a plain run times the K steps and prints the headline only)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step returned as DIR/loss.npy and '
+                    'DIR/seg_logit.npy (float32; at most 64 MB: the leading chunks of a larger batch)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -581,7 +610,7 @@ def main():
     _lib.lib()
     orig_affinity, affinity = pin_to_core_block(int(os.environ.get('LOCAL_RANK', '0')))
     rank, world, local = D.init_from_env()
-    side = (args.extras == 'all' or (args.extras == 'auto' and world == 1)) and not args.train_only  # B = 1 latency, fp32-MFMA step, 2D network, dense config
+    side = args.full and (args.extras == 'all' or (args.extras == 'auto' and world == 1)) and not args.train_only  # B = 1 latency, fp32-MFMA step, 2D network, dense config
     assert world == args.gpus, 'WORLD_SIZE ({}) != --gpus ({})'.format(world, args.gpus)
     local = int(os.environ.get('MVP_DEVICE', local))  # debugging aid: several ranks on one GPU (with MVP_DIST_BACKEND=gloo)
     if world > 1 and 'MVP_DEVICE' in os.environ:
@@ -618,11 +647,17 @@ def main():
     D.broadcast_parameters(model)
     weights = torch.linspace(0.5, 1.5, 20, device=dev)  # stands in for the class log-weights file (TRAIN.LABEL_WEIGHTS_PATH)
     loss_fn = SegLoss(weight=weights)
+    # Every step runs the optimizer at a learning rate of 0: the Adam launch reads and writes every parameter and both moments exactly as at
+    # the YAML's rate (the kernel has no branch on it), but the weights stay the seeded initial ones.  The step's cost does not depend on the
+    # weights' values, and what a step computes then depends on the seeded inputs alone -- with a real rate, the backward pass's float-atomic
+    # summation order (not fixed from run to run) moves the weights differently in every run and the dumped outputs of two runs disagree.
+    cfg.OPTIMIZER.BASE_LR = 0.0
     optimizer = C.build_optimizer(cfg, model)
     scheduler = C.build_scheduler(cfg, optimizer)
     grad_sync = D.GradSync(model.parameters()) if world > 1 else None
     timer = TimedLifting()
-    timer.install(model)
+    if args.full:  # (a plain run leaves the library calls of its steps unwrapped)
+        timer.install(model)
 
     from mvpnet_amd.mvpnet3d import prefetch_geometry
 
@@ -705,8 +740,8 @@ def main():
             os.path.basename(_lib.LIB_PATH), n, (time.perf_counter() - tp) / max(n, 1) * 1e3))
         return
 
-    settled = settle(eager_step, SETTLE_BLOCKS_MULTI if world > 1 else 0)   # set-up: the box and the allocator pools reach their steady state BEFORE the contract's warm-up
-    coll = collective_info(dev) if world > 1 else None
+    settled = settle(eager_step, SETTLE_BLOCKS_MULTI if world > 1 else SETTLE_BLOCKS)   # set-up: the box and the allocator pools reach their steady state BEFORE the contract's warm-up
+    coll = collective_info(dev) if (world > 1 and args.full) else None
     launch = resolve_launch(args, world)
     auto_probe = None
     if launch == 'auto':
@@ -767,7 +802,7 @@ def main():
     c0 = time.process_time()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, preds = step()
     if prof is not None:
         import pstats
         prof.disable()
@@ -778,11 +813,42 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
+        elapsed = tmax.item()
+    assert torch.isfinite(loss).item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, preds)
+    del preds  # (the last step's autograd graph is not kept alive into the measurements of --full)
+    out = {
+        'metric': 'chunks/sec (8192 pts, 3x160x120 views) fwd+bwd', 'value': round(args.batch * world * args.steps / elapsed, 3),
+        'unit': 'chunks/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': 'configs[2]: MVPNet lifting (unproject + pixel k-NN + gather) + FeatureAggregation + '
+                               'PN2SSG full train step (fwd+loss+bwd+Adam), 2D CNN replaced by a resident 64-ch feature map',
+                   'cfg': cfg_name, 'chunks_per_gpu': args.batch, 'points': 8192, 'views': '3x160x120', 'feature_channels': 64, 'k': 3,
+                   'parallelism': 'dp{} (one process per GPU, 1 grad all-reduce/step)'.format(world),
+                   'launch': 'hip graph (forward + backward; next-batch geometry {}), optimizer eager'.format(args.graph_geometry) if args.graph else 'eager',
+                   'launch_probe': auto_probe,
+                   'cpu_affinity': affinity,   # bench.pin_to_core_block: one block of an eighth of the host's cores per rank
+                   'settle_ms_per_step': settled,   # set-up blocks of 10 steps run BEFORE the warm-up (bench.settle): not part of W or K
+                   'learning_rate': 0.0,   # the full Adam update runs every step, the weights stay the seeded ones (see cfg.OPTIMIZER.BASE_LR above)
+                   'contraction': contraction_info()},
+        'host_enqueue_ms_per_step': round(host_elapsed / args.steps * 1e3, 3),
+        'host_cpu_ms_per_step': round(host_cpu / args.steps * 1e3, 3),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
     if args.graph:  # python does not run per replay: time the lifting call in a few eager steps right after the timed region
         for _ in range(5):
             eager_step()
         torch.cuda.synchronize()
-    assert torch.isfinite(loss).item()
     # spread: the same K steps twice more, untimed for `value` (the contract times exactly K steps above); reported beside it so a reader
     # sees what one 0.15 s measurement is worth on this box (box-to-box differences are larger: DESIGN.md section 5)
     repeats = [round(elapsed / args.steps * 1e3, 3)]
@@ -796,10 +862,6 @@ def main():
             repeats.append(round((time.perf_counter() - tr) / args.steps * 1e3, 3))
     timer.enabled = False   # (the repeats run exactly what the timed region ran, event pairs around the lifting call included)
     phases = phase_events() if (world == 1 and not args.graph and not args.host_profile) else None
-    if world > 1:
-        tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
-        elapsed = tmax.item()
 
     # The partition the reference actually trains with (mvpnet/train_mvpnet_3d.py:68-70: DataParallel splits the YAML's
     # TRAIN.BATCH_SIZE = 32 over the GPUs -> 32 / N chunks per GPU) next to the weak-scaling headline: what ONE step costs at 4 / 8 / 16
@@ -1055,22 +1117,9 @@ def main():
     dense = dense_extra(dev) if side else None
 
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
         lift_ms = timer.mean_ms()
         achieved = LIFT_BYTES_PER_CHUNK * args.batch / (lift_ms * 1e-3) / 1e9
-        out = {
-            'metric': 'chunks/sec (8192 pts, 3x160x120 views) fwd+bwd', 'value': round(args.batch * world * args.steps / elapsed, 3),
-            'unit': 'chunks/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': 'configs[2]: MVPNet lifting (unproject + pixel k-NN + gather) + FeatureAggregation + '
-                                   'PN2SSG full train step (fwd+loss+bwd+Adam), 2D CNN replaced by a resident 64-ch feature map',
-                       'cfg': cfg_name, 'chunks_per_gpu': args.batch, 'points': 8192, 'views': '3x160x120', 'feature_channels': 64, 'k': 3,
-                       'parallelism': 'dp{} (one process per GPU, 1 grad all-reduce/step)'.format(world),
-                       'launch': 'hip graph (forward + backward; next-batch geometry {}), optimizer eager'.format(args.graph_geometry) if args.graph else 'eager',
-                       'launch_probe': auto_probe,
-                       'cpu_affinity': affinity,   # bench.pin_to_core_block: one block of an eighth of the host's cores per rank
-                       'settle_ms_per_step': settled,   # set-up blocks of 10 steps run BEFORE the warm-up (bench.settle): not part of W or K
-                       'contraction': contraction_info()},
+        out.update({
             'collective': coll,
             'strong': strong,
             'per_gpu_batch': per_gpu_batch,
@@ -1079,8 +1128,6 @@ def main():
             'bf16_contraction': bf16_contraction,
             'bf16x6_backward': bf16x6_backward,
             'dense': dense,
-            'host_enqueue_ms_per_step': round(host_elapsed / args.steps * 1e3, 3),
-            'host_cpu_ms_per_step': round(host_cpu / args.steps * 1e3, 3),
             'phases': phases,
             'fwd_bwd_idle_us': None if phases is None else phases['fwd_bwd_idle_us'],
             'ms_per_step_repeats': repeats,
@@ -1093,7 +1140,7 @@ def main():
             'roofline': {'bound': 'hbm', 'kernel': 'mvp_lift_f32 = lift_prepare_kernel + lift_knn_gather_kernel',
                          'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4),
                          'traffic': lift_traffic(args.batch), 'traffic_source': 'profiles/{} (committed rocprofv3 PMC passes of this step at B=32, not read live)'.format(next((n for n in TRAFFIC_FILES if os.path.exists(os.path.join(ROOT, 'profiles', n))), 'none')), 'ms_per_launch': round(lift_ms, 4), 'algorithmic_bytes_per_launch': LIFT_BYTES_PER_CHUNK * args.batch},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             if orig_affinity is not None:
                 # the host baseline gets every core it had -- EVERY thread of the process: an affinity mask belongs to a thread, and torch's

@@ -67,6 +67,19 @@ def test_host_only_peer_ranks(graph):
     assert not [l for l in out.stdout.splitlines() if l.startswith('{')]  # peers print no result line
 
 
+def test_dump_outputs_stays_within_64_mb(tmp_path):
+    """--dump-outputs: float32 .npy files of what the timed step returned; a batch whose logits pass 64 MB is cut to its leading chunks."""
+    import numpy as np
+    import torch
+    import bench
+    logit = torch.randn(120, 20, 8192, generator=torch.Generator().manual_seed(0))   # 78.6 MB
+    bench.dump_outputs(str(tmp_path), torch.tensor(1.25), {'seg_logit': logit})
+    loss, got = np.load(tmp_path / 'loss.npy'), np.load(tmp_path / 'seg_logit.npy')
+    assert loss.dtype == np.float32 and float(loss) == 1.25
+    assert got.dtype == np.float32 and 90 <= got.shape[0] < 120 and np.array_equal(got, logit[:got.shape[0]].numpy())
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 * 10 ** 6
+
+
 def test_launch_mode_defaults():
     """--launch: eager for one rank, the probing mode for N > 1 (eight ranks share a host), --graph / --launch graph the replay; the peer ranks
     of tools/multi_rank_host.sh resolve it the same way (they mirror the probe's collectives)."""

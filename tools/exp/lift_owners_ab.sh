@@ -18,6 +18,6 @@ done
 cd $root
 for rep in 1 2 3; do
   for own in 1 2 4; do
-    MVP_LIBRARY=/tmp/libmvp_own$own.so python bench.py --no-cpu-baseline --train-only --steps 60 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('owners $own: lifting', d['roofline']['ms_per_launch'], 'ms in-step, frac', d['roofline']['frac'], 'step', d['ms_per_step'])"
+    MVP_LIBRARY=/tmp/libmvp_own$own.so python bench.py --full --no-cpu-baseline --train-only --steps 60 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('owners $own: lifting', d['roofline']['ms_per_launch'], 'ms in-step, frac', d['roofline']['frac'], 'step', d['ms_per_step'])"
   done
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6, first GPU call: suite state after the container re-creation, phase events of the eager step, bf16x6 backward, graph replay with / without the weight-gradient branch
 root=${GRAFT_REPO_ROOT:-$(pwd)}; out=$root/gpurun_out/r6_first; mkdir -p $out; cd $root
-MVP_BENCH_BF16X6_BWD=1 python bench.py --train-only --no-cpu-baseline --extras none > $out/bench_eager.json 2> $out/bench_eager.err
+MVP_BENCH_BF16X6_BWD=1 python bench.py --full --train-only --no-cpu-baseline --extras none > $out/bench_eager.json 2> $out/bench_eager.err
 python - <<PY
 import json; d=json.load(open('$out/bench_eager.json')); print('eager', d['ms_per_step'], d['ms_per_step_repeats'], d['host_enqueue_ms_per_step']); print(d['phases']); print(d['bf16x6_backward'])
 PY

@@ -1,7 +1,7 @@
 #!/bin/bash
 root=${GRAFT_REPO_ROOT:-$(pwd)}; out=$root/gpurun_out/r6_phases; mkdir -p $out; cd $root
 for b in 32 4; do
-python bench.py --train-only --no-cpu-baseline --extras none --batch $b > $out/bench_b$b.json 2> $out/bench_b$b.err
+python bench.py --full --train-only --no-cpu-baseline --extras none --batch $b > $out/bench_b$b.json 2> $out/bench_b$b.err
 python - <<PY
 import json; d=json.load(open('$out/bench_b$b.json')); print('B=$b eager', d['ms_per_step'], d['ms_per_step_repeats'], d['host_enqueue_ms_per_step']); print(json.dumps(d['phases'], indent=1))
 PY

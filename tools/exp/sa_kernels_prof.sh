@@ -11,4 +11,4 @@ for r in csv.DictReader(open(f)):
         print('{:8.1f} us x{:4d}  {}'.format(float(r['AverageNs'])/1e3, int(r['Calls']), r['Name'].replace('(anonymous namespace)::','').split('(')[0][:70]))
 print(json.load(open('$out/bench.json'))['ms_per_step'])
 PY
-for i in 1 2 3; do python bench.py --train-only --no-cpu-baseline --extras none --steps 40 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('step:', d['ms_per_step'], d['ms_per_step_repeats'])"; done
+for i in 1 2 3; do python bench.py --full --train-only --no-cpu-baseline --extras none --steps 40 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('step:', d['ms_per_step'], d['ms_per_step_repeats'])"; done

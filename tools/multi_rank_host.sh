@@ -23,7 +23,7 @@ for l in sys.stdin:
 ncores=$(nproc)
 echo "host cores: $ncores" >> $out
 make -C $root/mvpnet_amd/csrc noop > $root/gpurun_out/noop_build.log 2>&1 || echo "noop build FAILED" >> $out
-one() { MVP_CPU_AFFINITY=0 $3 python $root/bench.py --steps $steps --warmup 6 --no-cpu-baseline --train-only $2 2>/dev/null | line "$1"; }
+one() { MVP_CPU_AFFINITY=0 $3 python $root/bench.py --full --steps $steps --warmup 6 --no-cpu-baseline --train-only $2 2>/dev/null | line "$1"; }
 
 # ---- part 1: launch-only peers
 per=$((ncores / 8))
