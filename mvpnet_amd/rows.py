@@ -313,7 +313,6 @@ LINEAR_ASIDE = os.environ.get('MVP_LINEAR_ASIDE', '1') != '0'
 DW_FINISH_ON_LOAD = os.environ.get('MVP_DW_FINISH_ON_LOAD', '1') != '0'  # (A/B: the first layer's finish pass inside its weight-gradient launches)
 REL_DW_FUSED = os.environ.get('MVP_REL_DW_FUSED', '1') != '0'  # (A/B: FeatureAggregation's first-layer weight gradient, feature + relation columns, in ONE launch)
 REL_DW_SPLIT = os.environ.get('MVP_REL_DW_SPLIT', '1') != '0'  # (the relation columns' weight gradient on the calling stream at the end of the backward pass)  # (A/B switch: whole-weight linear layers' weight / bias gradients beside the chain)
-_EXP_SKIP_DW = os.environ.get('MVP_EXP_SKIP_DW', '0') == '1'
 
 
 class WeightUse:
@@ -410,10 +409,7 @@ class WeightGradSink:
     def run(self, dev, name, args, tensors, prec=None):
         if self.aside is None:
             self.aside = bool(DW_SIDE_STREAM and self.use is not None and self.use.aside_ok())
-        if self.aside:
-            side_stream.run(dev, name, args, [self.buf] + list(tensors), prec=prec)
-        else:
-            L.call(name, tensors[0], *args, prec=prec)
+        _weight_grad(self.aside, dev, name, args, tuple(tensors) + (self.buf,), prec)
 
     def done(self):
         """-> the gradient when this was the last user, else None."""
@@ -671,20 +667,24 @@ class DeferredFinish:
 
 
 class ActivationHandOver:
-    """Hand-over between two autograd nodes, the other way round from DeferredFinish: a shared-MLP chain (K = 1, no dropout) whose OUTPUT
-    a = relu(bn(y_L)) has exactly one consumer, a LinearRows node (the next propagation level's linear-first factorisation applies its first
-    layer to this level's output: pn2.FeaturePropagation).  The chain's backward starts with the gradient of that activation and needs,
-    before anything else, dz_L = g * [a > 0] and its two BatchNorm-backward column sums -- a pass over (g, y_L) and a reduction launch.
-    The input-gradient kernel of the consumer can do both in its epilogue (mvp_mlp_input_grad_f32 with y_prev: the form the chain uses
-    BETWEEN its own layers): the chain leaves (y_L, mean, invstd, gamma, beta) here in forward, the consumer's backward takes them, returns
-    dz_L instead of g and leaves the sums here; the chain's backward finds them and skips its own pass.  Only for outputs nobody else
-    reads (the caller guarantees it: PN2SSG wires the propagation levels, and not when anybody hooks the modules).
+    """Hand-over between two autograd nodes, the other way round from DeferredFinish: a shared-MLP chain (K = 1; a dropout behind its last
+    layer only when it is folded into the chain's own kernels) whose OUTPUT a = [keep *] relu(bn(y_L)) has exactly one consumer, a
+    LinearRows node (the next propagation level's linear-first factorisation applies its first layer to this level's output:
+    pn2.FeaturePropagation; the logit layer behind the segmentation head).  The chain's backward starts with the gradient of that activation
+    and needs, before anything else, dz_L = g * [a > 0] and its two BatchNorm-backward column sums -- a pass over (g, y_L) and a reduction
+    launch.  The input-gradient kernel of the consumer can do both in its epilogue (mvp_mlp_input_grad_f32 with y_prev: the form the chain
+    uses BETWEEN its own layers; mvp_mlp_input_grad_dropout_f32 behind a folded dropout): the chain leaves (y_L, mean, invstd, gamma, beta,
+    drop_p, drop_seed) here in forward, the consumer's backward takes them, returns dz_L instead of g and leaves the sums here; the chain's
+    backward finds them and skips its own pass.  Invariant: the consumer's input IS the chain's output, dropped out with exactly
+    (drop_p, drop_seed) when drop_p > 0 -- the consumer regenerates the keep mask from the pair, so nothing, F.dropout included, may sit
+    between the two nodes.  Only for outputs nobody else reads (the caller guarantees it: PN2SSG wires the propagation levels, and not
+    when anybody hooks the modules).
     MVP_ACT_HANDOVER=0: the chain's own pass (A/B switch)."""
     ENABLED = os.environ.get('MVP_ACT_HANDOVER', '1') != '0'
     __slots__ = ('info', 'stat')
 
     def __init__(self):
-        self.info = None   # set by the chain's forward: (y_L, mean, invstd, gamma, beta)
+        self.info = None   # set by the chain's forward: (y_L, mean, invstd, gamma, beta, drop_p, drop_seed); drop_p == 0: no dropout
         self.stat = None   # set by the consumer's backward: the two column sums of the dz_L it returned
 
 
@@ -871,15 +871,327 @@ def _bn_apply(y, mean, invstd, gamma, beta, G, K, C, relu, pool_sum=False):
     return out, arg
 
 
+_NONE4 = (None, None, None, None)
+
+
+def _mean_invstd(cout, dev):
+    return torch.empty(cout, dtype=torch.float32, device=dev), torch.empty(cout, dtype=torch.float32, device=dev)
+
+
+def _bn_tail(stat, part, eps, mom, mean, invstd, bn):
+    return (L.ptr(stat), L.ptr(part), float(eps), float(mom), L.ptr(mean), L.ptr(invstd), L.ptr(bn[0]), L.ptr(bn[1]), L.ptr(bn[2]))
+
+
+def _fwd_stats(y, stat, R, cout, training, bn, eps, mom):
+    """-> (mean, invstd) of a layer whose column sums are in `stat`: mvp_bn_finalize_f32 in training mode, else the running statistics."""
+    if not training:
+        return bn[0], eval_invstd.get(bn[1], eps)
+    mean, invstd = _mean_invstd(cout, y.device)
+    L.call('mvp_bn_finalize_f32', y, L.ptr(stat), R, cout, float(eps), float(mom), L.ptr(mean), L.ptr(invstd), L.ptr(bn[0]), L.ptr(bn[1]), L.ptr(bn[2]))
+    return mean, invstd
+
+
+def _fwd_given(x0, training, first_stat, stat, bn, eps, mom):
+    """w is None: x0 already IS the layer's pre-BN output.  first_stat: None, its column sums, or (stat, mean | invstd) already finalized."""
+    R, cout = x0.shape
+    if training and isinstance(first_stat, tuple):
+        return x0, first_stat[1][:cout], first_stat[1][cout:]
+    if training and first_stat is not None:
+        stat = first_stat
+    elif training:
+        L.call('mvp_colstats_f32', x0, L.ptr(x0), R, cout, L.ptr(stat), L.ptr(_cs_partial(R, cout, x0.device)))
+    return (x0,) + _fwd_stats(x0, stat, R, cout, training, bn, eps, mom)
+
+
+def _fwd_rel(x, rel, w, wrel, training, stat, bn, eps, mom, prec):
+    """First layer over [x | rel]: the last four columns of w (`wrel`) meet `rel` in the kernel's epilogue (mvp_mlp_forward_rel_bn_f32)."""
+    R, cin_f = x.shape
+    cout, cin = w.size(0), w.size(1)
+    assert cin == cin_f + 4
+    y = torch.empty((R, cout), dtype=torch.float32, device=x.device)
+    mean, invstd = _mean_invstd(cout, x.device) if training else (None, None)
+    tail = _bn_tail(stat, _partial(R, cout, x.device), eps, mom, mean, invstd, bn) if training else (None, None, 0.0, 0.0, None, None, None, None, None)
+    L.call('mvp_mlp_forward_rel_bn_f32', x, L.ptr(x), R, cin_f, cin_f, L.ptr(w), cin, cout, L.ptr(rel), L.ptr(wrel), L.ptr(y), *tail, prec=prec)
+    return (y, mean, invstd) if training else (y,) + _fwd_stats(y, None, R, cout, False, bn, eps, mom)
+
+
+def _fwd_pool(x, w, act, gamma, beta, K, stat, bn, eps, mom, prec):
+    """POOL_WITHOUT_Y last layer -> (ysel, mean, invstd, out, arg); ysel (G, cout), the pre-BN value behind each pooled output, stands in for y_L."""
+    R, dev = x.size(0), x.device
+    cout, cin = w.size(0), w.size(1)
+    G = R // K
+    mean, invstd = _mean_invstd(cout, dev)
+    ymax, ymin, out, ysel = (torch.empty((G, cout), dtype=torch.float32, device=dev) for _ in range(4))
+    amax, amin, arg = (torch.empty((G, cout), dtype=torch.uint8, device=dev) for _ in range(3))
+    part = torch.empty(((R + 127) // 128) * 2 * cout, dtype=torch.float64, device=dev)
+    L.call('mvp_mlp_forward_pool_f32', x, L.ptr(x), R, cin, x.size(1), L.ptr(w), cin, cout, *act, L.ptr(ymax), L.ptr(ymin), L.ptr(amax), L.ptr(amin),
+           *_bn_tail(stat, part, eps, mom, mean, invstd, bn), prec=prec)
+    L.call('mvp_pool_finalize_f32', ymax, L.ptr(ymax), L.ptr(ymin), L.ptr(amax), L.ptr(amin), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+           G, cout, 1, L.ptr(out), L.ptr(arg), L.ptr(ysel))
+    return ysel, mean, invstd, out, arg
+
+
+def _fwd_layer(x, w, act, training, stat, bn, eps, mom, prec):
+    """Training: forward + batch statistics + BatchNorm finalize in one call (mvp_mlp_forward_bn_f32); eval mode or no rows: the plain
+    forward (mvp_mlp_forward_f32), then the statistics on their own."""
+    R, dev = x.size(0), x.device
+    cout, cin = w.size(0), w.size(1)
+    y = torch.empty((R, cout), dtype=torch.float32, device=dev)
+    if training and R > 0:
+        mean, invstd = _mean_invstd(cout, dev)
+        L.call('mvp_mlp_forward_bn_f32', x, L.ptr(x), R, cin, x.size(1), L.ptr(w), cin, cout, *act, L.ptr(y),
+               *_bn_tail(stat, _partial(R, cout, dev), eps, mom, mean, invstd, bn), prec=prec)
+        return y, mean, invstd
+    L.call('mvp_mlp_forward_f32', x, L.ptr(x), R, cin, x.size(1), L.ptr(w), cin, cout, *act, None, L.ptr(y), L.ptr(stat),
+           L.ptr(_partial(R, cout, dev) if training else None), prec=prec)
+    return (y,) + _fwd_stats(y, stat, R, cout, training, bn, eps, mom)
+
+
+def _weight_grad(aside, dev, name, args, keep, prec=None):
+    """One weight-gradient launch beside the chain (SideStream; `keep`: EVERYTHING the kernel touches, alive until the join: ADVICE r5) or on it."""
+    if aside:
+        side_stream.run(dev, name, args, keep, prec=prec)
+    else:
+        L.call(name, keep[0], *args, prec=prec)
+
+
+def _backward_route(prec, reproducible, R, i, w, y, src, gcur, pending, rel, need_dz, pool_here, defer_open, must_wide):
+    """The route of layer i in MLPChainRows.backward (the table in its docstring).  Decides only: no launch, no allocation, no mutation.
+    pool_here: the layer's output exists pooled only; defer_open: a DeferredFinish waits for dz_0; must_wide: the head started in mode 2."""
+    fin = pending is not None
+    if w is None:
+        return 'defer' if (fin and defer_open) else 'given'
+    cout, cin, ldx = y.size(1), w.size(1), src.size(1)
+    wide = bool(i > 0 and not pool_here and rel is None and need_dz and wide_backward_ok(prec, R, cout, cin, ldx) and aligned16(gcur, y, src))
+    assert wide or not must_wide
+    if wide:
+        return 'wide'
+    if rel is not None:
+        if (fin and DW_FINISH_ON_LOAD and i == 0 and not need_dz and prec[0] != 0 and prec[1] in (1, 3) and cout % 4 == 0 and cout > 32 and ldx > 32 and
+                ldx == cin - 4 and aligned16(gcur, y) and max(cout, ldx) >= L.mlp_min_width()):
+            return 'rel_finish_one' if (REL_DW_FUSED and not reproducible and 32 < ldx <= 64 and aligned16(src, rel)) else 'rel_finish'
+        return 'rel'
+    if pool_here or (prec[0] != 0 and cout <= FUSE_BWD_MAX_COUT and cin <= FUSE_BWD_MAX_CIN and (not need_dz or cin % 4 == 0) and
+                     (i > 0 or ldx == cin or not need_dz)):
+        return 'fuse'
+    if (i > 0 and need_dz and not reproducible and dx_wide_ok(prec, R, cout, cin, ldx, fin) and aligned16(gcur, y, src) and w.is_contiguous()):
+        return 'dxw'
+    return 'tile'
+
+
+class _ChainWalk:
+    """MLPChainRows.backward's saved tensors, arenas and one launcher per route.  The walking state (gcur, pending): `gcur` is either dy_i
+    itself (pending is None) or dz_i = the gradient w.r.t. layer i's ACTIVATION already masked by its ReLU, with `pending` = its two
+    BatchNorm-backward column sums: the "finish" (dz_i -> dy_i) then happens INSIDE the layer's kernels, or as its own pass (`finish`).
+    A launcher returns (gcur, pending) for layer i - 1 (at i == 0: the input's gradient or None), then dW_i, dgamma_i, dbeta_i (None: no
+    finish inside)."""
+    __slots__ = ('ctx', 'nl', 'training', 'K', 'R', 'ys', 'params', 'bn', 'bnp', 'prec', 'dev', 'dw_aside', 'dw_arena', 'st_arena', 'dw_off', 'st_off',
+                 'pool', 'last_wide')
+
+    def __init__(self, ctx, ys, means, invstds, params, dev):
+        self.ctx, self.prec = ctx, tuple(ctx.prec)
+        self.nl, self.training, self.K, self.R = ctx.cfg
+        self.ys, self.params, self.dev = ys, params, dev
+        # per layer: (y, mean, invstd, gamma, beta), as tensors (what a side-stream launch keeps alive) and as pointers
+        self.bn = [(ys[i], means[i], invstds[i], params[3 * i + 1], params[3 * i + 2]) for i in range(self.nl)]
+        self.bnp = [tuple(L.ptr(t) for t in b) for b in self.bn]
+        self.dw_aside = bool(DW_SIDE_STREAM and ctx.dw_use is not None and ctx.dw_use.aside_ok())
+        self.pool, self.last_wide = None, False
+        # `dW` and `stat` are accumulated into by the kernels: two zeroed arenas for the whole chain
+        ws = [params[3 * i] for i in range(self.nl)]
+        self.dw_arena = zero_pool.zeros(sum(0 if w is None else w.numel() for w in ws), torch.float32, self.dev)
+        self.st_arena = zero_pool.zeros(2 * sum(w.size(1) for w in ws[1:]), torch.float64, self.dev)
+        self.dw_off = self.st_off = 0
+
+    def outputs(self, i, w, need_dz=False, fin=False):
+        """-> (dW_i, column sums of dz_{i-1} [arena slices; no sums at i == 0], dz_{i-1} [when needed], dgamma_i, dbeta_i [with a finish inside])."""
+        cout, cin = w.size(0), w.size(1)
+        off, st = self.dw_off, None
+        self.dw_off = off + cout * cin
+        if i > 0:
+            st = self.st_arena[self.st_off:self.st_off + 2 * cin]
+            self.st_off += 2 * cin
+        dz = torch.empty((self.R, cin), dtype=torch.float32, device=self.dev) if need_dz else None
+        dgb = torch.empty((2, cout), dtype=torch.float32, device=self.dev) if fin else (None, None)
+        return self.dw_arena[off:off + cout * cin].view(cout, cin), st, dz, dgb[0], dgb[1]
+
+    def head(self, g, out, arg):
+        """grad_out -> the walking state at the last layer: (gcur, pending, dgamma_L, dbeta_L).  Sets `pool` (the last layer's output exists
+        pooled only) and `last_wide` (gcur is the gradient of its dropped-out / pooled activation: mode 2 of the wide backward)."""
+        ctx, nl, K, R, ys, dev = self.ctx, self.nl, self.K, self.R, self.ys, self.dev
+        y, mean, invstd, gamma, beta = self.bn[-1]
+        py, pmean, pinvstd, pgamma, pbeta = self.bnp[-1]
+        cl, G, training = y.size(1), R // K, int(self.training)
+        drop_p, drop_seed = ctx.dropout
+        if ctx.act_out is not None and ctx.act_out.stat is not None:
+            # (ActivationHandOver: the consumer already applied the ReLU mask and summed the columns, g IS dz_L)
+            handed, ctx.act_out.stat = ctx.act_out.stat, None
+            return g, handed, None, None
+        wl = self.params[3 * (nl - 1)]
+        wide = bool(not ctx.pooled and nl >= 2 and wl is not None and g.is_cuda and R * cl < 2 ** 32 and aligned16(g, y, ys[nl - 2]) and
+                    wide_backward_ok(self.prec, R, wl.size(0), wl.size(1), ys[nl - 2].size(1)))
+        wide_sum = wide and WIDE_BWD_POOLED and K > 1 and arg is None and drop_p == 0
+        self.last_wide = wide = wide_sum or (wide and K == 1)
+        if not (ctx.pooled or wide or drop_p > 0):
+            dy, dgam, dbet = _bn_backward(g, out, arg, y, mean, invstd, gamma, beta, G, K, cl, True, self.training)
+            return dy, None, dgam, dbet
+        stat = torch.empty(2 * cl, dtype=torch.float64, device=dev)
+        if ctx.pooled:
+            # (the column sums come from the (G, cl) tensors, dy_L is formed inside the one-kernel layer backward from the re-computed y_L)
+            L.call('mvp_pool_backward_stats_f32', g, L.ptr(g), L.ptr(out), py, pmean, pinvstd, G, cl, 1, L.ptr(stat), L.ptr(_cs_partial(G, cl, dev)))
+            self.pool = (g, out, arg)
+            return None, stat, None, None
+        if wide_sum:
+            # (in front of a SUM over K: the wide backward reads row r / K of the POOLED output's gradient; only the column sums of dz_L here)
+            L.call('mvp_bn_rows_backward_f32', g, L.ptr(g), None, None, py, pmean, pinvstd, pgamma, pbeta, G, K, cl, 1, training, L.ptr(stat),
+                   None, None, None, L.ptr(_cs_partial(R, cl, dev)))
+            return g, stat, None, None
+        # (wide: only the column sums of dz_L = g * keep * relu'(bn(y_L)) here, no dy_L tensor; else dy_L, keep mask regenerated from (p, seed))
+        dy = None if wide else torch.empty_like(y)
+        dgam, dbet = (None, None) if wide else torch.empty((2, cl), dtype=torch.float32, device=dev)
+        L.call('mvp_bn_rows_backward_dropout_f32', g, L.ptr(g), py, pmean, pinvstd, pgamma, pbeta, R, cl, 1, training, L.ptr(stat), L.ptr(dy),
+               L.ptr(dgam), L.ptr(dbet), L.ptr(_cs_partial(R, cl, dev)), drop_p, drop_seed)
+        return (g, stat, None, None) if wide else (dy, None, dgam, dbet)
+
+    def finish(self, i, gcur, pending):
+        """dz_i -> dy_i as its own pass, for the routes whose kernels cannot do it: -> (dy_i, dgamma_i, dbeta_i)."""
+        cout = self.ys[i].size(1)
+        dy = torch.empty((self.R, cout), dtype=torch.float32, device=self.dev)
+        dgam, dbet = torch.empty((2, cout), dtype=torch.float32, device=self.dev)
+        L.call('mvp_bn_rows_backward_finish_f32', gcur, L.ptr(gcur), *self.bnp[i], self.R, cout, int(self.training), L.ptr(pending), L.ptr(dy),
+               L.ptr(dgam), L.ptr(dbet))
+        return dy, dgam, dbet
+
+    def defer(self, gcur, pending, defer):
+        """dz_0 goes back unfinished to an accepting DeferredFinish; dgamma / dbeta are the two column sums."""
+        defer.info = self.bn[0][:4] + (pending, self.training)
+        dgb = pending.view(2, self.ys[0].size(1)).to(torch.float32)
+        return gcur, None, None, dgb[1], dgb[0]
+
+    def rel(self, gcur, pending, w, src, need_dz, route):
+        """First layer over [x | rel]: dW's feature and relation columns from two launches, the input gradient (when needed) from the weight's
+        feature columns.  route 'rel_finish': the weight-gradient launches form dy_0 from (dz_0, y_0) while they load it -- no finish pass (95 us
+        at the very end of the training stream), no dy tensor; 'rel_finish_one': both column groups in one launch (0.6 GB read, not 1.0)."""
+        R, (rel, w0_param), dev = self.R, self.ctx.rel, self.dev
+        cout, cin, cin_f = w.size(0), w.size(1), src.size(1)
+        dw, dz, dgam, dbet = self.outputs(0, w)[0], None, None, None
+        if route != 'rel':
+            dbet, dgam = pending.view(2, cout).to(torch.float32)
+            fin = (L.ptr(gcur),) + self.bnp[0][:4] + (L.ptr(pending), int(self.training))
+            ws = L.current_dw_workspace(dev)
+        if route == 'rel_finish_one':
+            L.call('mvp_mlp_weight_grad_finish_rel_p_f32', gcur, *fin, L.ptr(src), R, cout, cin_f, cin_f, L.ptr(rel), L.ptr(dw), L.ptr_at(dw, cin_f), cin,
+                   *self.prec)
+            return None, None, dw, dgam, dbet
+        for xs, ncol, c0 in ((src, cin_f, 0), (rel, 4, cin_f)):
+            if route == 'rel':
+                # (REL_DW_SPLIT: at the END of the backward pass the relation columns run ON the calling stream, the two launches overlap)
+                args = (L.ptr(gcur), L.ptr(xs), R, cout, ncol, ncol, None, None, None, None, L.ptr_at(dw, c0), cin)
+                _weight_grad(self.dw_aside and not (REL_DW_SPLIT and xs is rel and not need_dz), dev, 'mvp_mlp_weight_grad_f32', args, (gcur, xs, dw), self.prec)
+            else:
+                _weight_grad(self.dw_aside and xs is not rel and ws[0] is None, dev, 'mvp_mlp_weight_grad_finish_p_f32',
+                             fin + (L.ptr(xs), R, cout, ncol, ncol, L.ptr_at(dw, c0), cin) + ws + self.prec, (gcur, src, dw, pending) + self.bn[0][:4])
+        if route == 'rel' and need_dz:
+            dz = torch.empty((R, cin_f), dtype=torch.float32, device=dev)
+            wf = weight_slices.get(w0_param, 0, cin_f, cin_f)
+            L.call('mvp_mlp_input_grad_f32', gcur, L.ptr(gcur), R, cout, L.ptr(wf), cin_f, None, None, None, None, None, L.ptr(dz), None, None, prec=self.prec)
+        return dz, None, dw, dgam, dbet
+
+    def tile_weight_grad(self, i, gcur, w, src, dw):
+        args = (L.ptr(gcur), L.ptr(src), self.R, w.size(0), w.size(1), src.size(1)) + (self.bnp[i - 1][1:] if i else _NONE4) + (L.ptr(dw), w.size(1))
+        _weight_grad(self.dw_aside, self.dev, 'mvp_mlp_weight_grad_f32', args, (gcur, src, dw) + (self.bn[i - 1][1:] if i else ()), self.prec)
+
+    def dxw(self, i, gcur, pending, w, src):
+        """Input gradient in one pass (finish of dz_i on load when pending), the weight gradient with the same finish on load: no dy_i tensor."""
+        R, dev, fin = self.R, self.dev, pending is not None
+        cout, cin, ldx = w.size(0), w.size(1), src.size(1)
+        actp, finp = self.bnp[i - 1][1:], self.bnp[i][:4] if fin else _NONE4
+        dw, stat, dz, dgam, dbet = self.outputs(i, w, True, fin)
+        if not fin:
+            self.tile_weight_grad(i, gcur, w, src, dw)
+        else:
+            args = (L.ptr(gcur),) + finp + (L.ptr(pending), int(self.training), L.ptr(src), R, cout, cin, ldx) + actp + (L.ptr(dw), cin, None, 0) + self.prec
+            _weight_grad(self.dw_aside, dev, 'mvp_mlp_weight_grad_finish_act_p_f32', args, (gcur,) + self.bn[i][:4] + (pending, src, dw) + self.bn[i - 1][1:])
+        nbytes = int(L.lib().mvp_mlp_input_grad_wide_workspace_bytes(cout, cin))
+        wimg = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.call('mvp_mlp_input_grad_wide_f32', gcur, L.ptr(gcur), *finp, L.ptr(pending), L.ptr(dgam), L.ptr(dbet), int(self.training), L.ptr(src), ldx, *actp,
+               L.ptr(w), cin, R, cout, cin, L.ptr(dz), L.ptr(stat), L.ptr(wimg), nbytes, prec=self.prec)
+        return dz, stat, dw, dgam, dbet
+
+    def wide(self, i, gcur, pending, w, src):
+        """mode 0: gcur is dy_i; 1: dz_i (finish inside); 2: the gradient of the last layer's dropped-out / summed-over-K activation."""
+        cout, cin, fin = w.size(0), w.size(1), pending is not None
+        last = self.last_wide and i == self.nl - 1
+        mode = (2 if last else 1) if fin else 0
+        drop_p, drop_seed = self.ctx.dropout if mode == 2 else (0.0, 0)
+        dw, stat, dz, dgam, dbet = self.outputs(i, w, True, fin)
+        ticket = zero_pool.zeros(2, torch.int32, self.dev)
+        L.call('mvp_mlp_layer_backward_wide_pooled_f32', src, L.ptr(gcur), *(self.bnp[i][:4] if fin else _NONE4), self.bnp[i][4] if mode == 2 else None,
+               L.ptr(pending), L.ptr(dgam), L.ptr(dbet), int(self.training), mode, self.K if last else 1, float(drop_p), int(drop_seed), L.ptr(src),
+               src.size(1), *self.bnp[i - 1][1:], L.ptr(w), cin, self.R, cout, cin, L.ptr(dw), cin, L.ptr(dz), L.ptr(stat), L.ptr(ticket),
+               *L.current_dw_workspace(self.dev), prec=self.prec)
+        return dz, stat, dw, dgam, dbet
+
+    def fuse(self, i, gcur, pending, w, src, need_dz):
+        """gcur None: the pooled front end -- y_L re-computed from the layer's input, dy_L formed from the pooled output's gradient."""
+        R, cout, cin, fin = self.R, w.size(0), w.size(1), pending is not None
+        fy, fm, fi, fg = self.bnp[i][:4] if fin else _NONE4
+        dw, stat, dz, dgam, dbet = self.outputs(i, w, need_dz, fin)
+        part = torch.empty(L.lib().mvp_mlp_layer_backward_partial_count(R, cin), dtype=torch.float64, device=self.dev) if (i > 0 and need_dz) else None
+        pg, po, pa = (None, None, None) if gcur is not None else self.pool
+        L.call('mvp_mlp_layer_backward_f32', src, L.ptr(gcur), fy if gcur is not None else None, fm, fi, fg, L.ptr(pending), L.ptr(dgam), L.ptr(dbet),
+               int(self.training), L.ptr(src), src.size(1), *(self.bnp[i - 1][1:] if i else _NONE4), L.ptr(w), cin, R, cout, cin, L.ptr(dw), cin, L.ptr(dz),
+               L.ptr(stat), L.ptr(part), L.ptr(pg), L.ptr(po), L.ptr(pa), prec=self.prec)
+        return dz, stat, dw, dgam, dbet
+
+    def tile(self, i, gcur, w, src, need_dz):
+        """Weight gradient, then input gradient = dy . W with the previous layer's ReLU mask and BN-backward column sums in the epilogue."""
+        dw, stat, dz, _, _ = self.outputs(i, w, need_dz)
+        self.tile_weight_grad(i, gcur, w, src, dw)
+        if need_dz:
+            L.call('mvp_mlp_input_grad_f32', gcur, L.ptr(gcur), self.R, w.size(0), L.ptr(w), w.size(1), *(self.bnp[i - 1] if i else (None,) * 5), L.ptr(dz),
+                   L.ptr(stat), L.ptr(_partial(self.R, w.size(1), self.dev) if i > 0 else None), prec=self.prec)
+        return dz, stat, dw, None, None
+
+
 class MLPChainRows(torch.autograd.Function):
     """A whole SharedMLP (conv1x1 + BN + ReLU per layer, optional max over K after the last) as ONE autograd
     node on rows.  Forward: one fp32-MFMA kernel per layer (mvp_mlp_forward_f32) that applies the previous
     layer's BN+ReLU while loading and emits this layer's batch statistics from its epilogue, so only the
-    pre-BN outputs y_i ever reach HBM.  Backward re-creates each activation from y_i on the fly."""
+    pre-BN outputs y_i ever reach HBM.  Backward re-creates each activation from y_i on the fly.
+
+    Backward walks the layers from the last to the first (_ChainWalk); _backward_route picks, per layer, the first route whose condition holds:
+
+    route           entry point(s)                               condition
+    defer           (none)                                       w is None, finish pending, an accepting DeferredFinish: dz_0 goes back unfinished
+    given           [finish]                                     w is None otherwise: dy_0 is the input's gradient
+    wide            mvp_mlp_layer_backward_wide_pooled_p         i > 0, not a pooled last layer, no rel, wide_backward_ok (65..128 channels, or
+                                                                 64 -> 64 over very many rows), 16-byte aligned; REQUIRED after a mode-2 head
+    rel_finish_one  mvp_mlp_weight_grad_finish_rel_p             first layer over [x | rel], finish pending, x needs no gradient, split-bf16 (1 or 3
+                                                                 pieces), > 32 channels, aligned (DW_FINISH_ON_LOAD); and 33..64 feature columns,
+                                                                 not reproducible mode (REL_DW_FUSED)
+    rel_finish      2 x mvp_mlp_weight_grad_finish_p             the same without the last line (feature columns beside the chain)
+    rel             [finish], 2 x mvp_mlp_weight_grad_p,         first layer over [x | rel] otherwise
+                    mvp_mlp_input_grad_p when x needs it
+    fuse            mvp_mlp_layer_backward_p (_ws_p)             the last layer of a POOL_WITHOUT_Y chain (the kernel's pooled front end); or split-bf16,
+                                                                 cout <= FUSE_BWD_MAX_COUT, cin <= FUSE_BWD_MAX_CIN, cin % 4 == 0 and (at i == 0)
+                                                                 an unpadded input when an input gradient is needed
+    dxw             mvp_mlp_weight_grad_finish_act_p (or         i > 0, DX_WIDE and dx_wide_ok (whole 64 x 128 weight blocks), aligned, contiguous
+                    _weight_grad_p), mvp_mlp_input_grad_wide_p   weight, not reproducible mode
+    tile            [finish], mvp_mlp_weight_grad_p (_ws_p),     everything else
+                    mvp_mlp_input_grad_p when needed
+    [finish] = mvp_bn_rows_backward_finish_f32 when a finish is pending.  Weight-gradient launches run beside the chain when DW_SIDE_STREAM
+    and the chain's WeightUse allow it.  Before the walk, _ChainWalk.head turns grad_out into the state at the last layer: sums handed over by
+    the consumer (ActivationHandOver: none), pooled (mvp_pool_backward_stats), sum over K / K == 1 in front of a `wide` layer
+    (mvp_bn_rows_backward / _backward_dropout, column sums only: mode 2), folded dropout (mvp_bn_rows_backward_dropout), plain
+    (mvp_bn_rows_backward)."""
 
     @staticmethod
-    def forward(ctx, x0, training, K, eps_mom, bn_buffers, first_stat, pool_sum, *params):
+    def forward(ctx, x0, training, K, eps_mom, bn_buffers, first_stat, opts, *params):
         # params = (W_1, gamma_1, beta_1, ..., W_L, gamma_L, beta_L); bn_buffers = [(running_mean, running_var, num_batches_tracked or None)] * L
+        # opts: {'sum' (sum over K instead of max), 'drop_p', 'drop_seed' (dropout behind the last layer, K = 1: SharedMLPDO), 'use' (WeightUse:
+        # the weight gradients may run on the side stream, see SideStream), 'defer' (DeferredFinish), 'act_out' (ActivationHandOver),
+        # 'rel': (rel (R,4), first conv weight) -- the first layer's input is [x0 | rel] without the concatenated tensor}
         nl = len(params) // 3
         R = x0.size(0)
         dev = x0.device
@@ -887,21 +1199,13 @@ class MLPChainRows(torch.autograd.Function):
         # as arguments -- also to the backward's, which autograd issues from its own thread (a forward under
         # _lib.mlp_precision(...) used to get the process default in backward)
         prec = ctx.prec = L.current_precision()
-        # pool_sum: plain bool, or a dict of options {'sum', 'drop_p', 'drop_seed' (dropout behind the last layer, K = 1: SharedMLPDO),
-        # 'use' (WeightUse: the weight gradients may run on the side stream, see SideStream)}
-        opts = pool_sum if isinstance(pool_sum, dict) else {'sum': bool(pool_sum)}
         drop_p, drop_seed = opts.get('drop_p', 0.0), opts.get('drop_seed', 0)
         ctx.dw_use = opts.get('use')
         ctx.defer = opts.get('defer')
         pool_sum = bool(opts.get('sum', False))
-        # 'rel': (rel (R,4), first conv weight): the first layer's input is [x0 | rel] without the concatenated tensor -- its weight has
-        # x0.size(1) + 4 columns, the last four meet `rel` in the kernel's epilogue (mvp_mlp_forward_rel_bn_f32)
-        rel, w0_param = opts.get('rel', (None, None))
-        ctx.rel = (rel, w0_param)
+        rel, w0_param = ctx.rel = opts.get('rel', (None, None))
         ctx.dropout = (float(drop_p), int(drop_seed))
         ys, means, invstds = [], [], []
-        act = (None, None, None, None)
-        x = x0
         couts = [x0.size(1) if params[3 * i] is None else params[3 * i].size(0) for i in range(nl)]
         # the kernels ADD their column sums to `stat`: one zeroed arena for the whole chain instead of a memset per layer
         # (+ 1 per layer: the completion counter of the "last workgroup finalizes" reduction lives behind the layer's sums)
@@ -910,106 +1214,25 @@ class MLPChainRows(torch.autograd.Function):
         pooled = bool(POOL_WITHOUT_Y and training and K == 32 and not pool_sum and nl >= 2 and wl is not None and R % 32 == 0 and R >= 32768 and
                       prec[0] != 0 and wl.size(0) <= min(64, FUSE_BWD_MAX_COUT) and wl.size(1) <= 64 and
                       wl.size(0) % 4 == 0 and wl.size(1) % 4 == 0)
-        off = 0
+        x, act, off = x0, _NONE4, 0  # act: the previous layer's (mean, invstd, gamma, beta) as pointers, applied by the next kernel while it loads x
         for i in range(nl):
             w, gamma, beta = params[3 * i], params[3 * i + 1], params[3 * i + 2]
             eps, mom = eps_mom[i]
             stat = arena[off:off + 2 * couts[i] + 1] if training else None
             off += 2 * couts[i] + 1
-            if w is None:  # x0 already IS this layer's pre-BN output (the linear part ran before the grouping)
+            if w is None:
                 assert i == 0
-                cout = x0.size(1)
-                y = x0
-                if training and isinstance(first_stat, tuple):  # ... and finalized the BatchNorm on its reduction: (stat, mean | invstd)
-                    first_mi = first_stat[1]
-                    ys.append(y)
-                    means.append(first_mi[:cout])
-                    invstds.append(first_mi[cout:])
-                    act = (means[-1], invstds[-1], gamma, beta)
-                    x = y
-                    continue
-                if training and first_stat is not None:
-                    stat = first_stat  # the grouping kernel already summed the columns
-                elif training:
-                    L.call('mvp_colstats_f32', y, L.ptr(y), R, cout, L.ptr(stat), L.ptr(_cs_partial(R, cout, dev)))
+                y, mean, invstd = _fwd_given(x0, training, first_stat, stat, bn_buffers[i], eps, mom)
+            elif i == 0 and rel is not None:
+                y, mean, invstd = _fwd_rel(x, rel, w, weight_slices.get(w0_param, x0.size(1), w.size(1), 4), training, stat, bn_buffers[i], eps, mom, prec)
+            elif pooled and i == nl - 1:
+                y, mean, invstd, out, arg = _fwd_pool(x, w, act, gamma, beta, K, stat, bn_buffers[i], eps, mom, prec)
             else:
-                cout, cin = w.size(0), w.size(1)
-                if i == 0 and rel is not None:
-                    cin_f = x0.size(1)
-                    assert cin == cin_f + 4 and act[0] is None
-                    wrel = weight_slices.get(w0_param, cin_f, cin, 4)
-                    rm, rv, nbt = bn_buffers[i]
-                    y = torch.empty((R, cout), dtype=torch.float32, device=dev)
-                    if training:
-                        mean = torch.empty(cout, dtype=torch.float32, device=dev)
-                        invstd = torch.empty(cout, dtype=torch.float32, device=dev)
-                        L.call('mvp_mlp_forward_rel_bn_f32', x, L.ptr(x), R, cin_f, cin_f, L.ptr(w), cin, cout, L.ptr(rel), L.ptr(wrel), L.ptr(y),
-                               L.ptr(stat), L.ptr(_partial(R, cout, dev)), float(eps), float(mom), L.ptr(mean), L.ptr(invstd), L.ptr(rm), L.ptr(rv),
-                               L.ptr(nbt), prec=prec)
-                    else:
-                        L.call('mvp_mlp_forward_rel_bn_f32', x, L.ptr(x), R, cin_f, cin_f, L.ptr(w), cin, cout, L.ptr(rel), L.ptr(wrel), L.ptr(y),
-                               None, None, 0.0, 0.0, None, None, None, None, None, prec=prec)
-                        mean, invstd = rm, eval_invstd.get(rv, eps)
-                    ys.append(y)
-                    means.append(mean)
-                    invstds.append(invstd)
-                    act = (mean, invstd, gamma, beta)
-                    x = y
-                    continue
-                if pooled and i == nl - 1:
-                    # last layer of a set-abstraction MLP: batch statistics + per-ball max / min of the pre-BN output, no (R, cout) tensor
-                    G = R // K
-                    rm, rv, nbt = bn_buffers[i]
-                    mean = torch.empty(cout, dtype=torch.float32, device=dev)
-                    invstd = torch.empty(cout, dtype=torch.float32, device=dev)
-                    ymax = torch.empty((G, cout), dtype=torch.float32, device=dev)
-                    ymin = torch.empty((G, cout), dtype=torch.float32, device=dev)
-                    amax = torch.empty((G, cout), dtype=torch.uint8, device=dev)
-                    amin = torch.empty((G, cout), dtype=torch.uint8, device=dev)
-                    L.call('mvp_mlp_forward_pool_f32', x, L.ptr(x), R, cin, x.size(1), L.ptr(w), cin, cout, L.ptr(act[0]), L.ptr(act[1]),
-                           L.ptr(act[2]), L.ptr(act[3]), L.ptr(ymax), L.ptr(ymin), L.ptr(amax), L.ptr(amin), L.ptr(stat),
-                           L.ptr(torch.empty(((R + 127) // 128) * 2 * cout, dtype=torch.float64, device=dev)), float(eps), float(mom),
-                           L.ptr(mean), L.ptr(invstd), L.ptr(rm), L.ptr(rv), L.ptr(nbt), prec=prec)
-                    out = torch.empty((G, cout), dtype=torch.float32, device=dev)
-                    arg = torch.empty((G, cout), dtype=torch.uint8, device=dev)
-                    ysel = torch.empty((G, cout), dtype=torch.float32, device=dev)
-                    L.call('mvp_pool_finalize_f32', ymax, L.ptr(ymax), L.ptr(ymin), L.ptr(amax), L.ptr(amin), L.ptr(mean), L.ptr(invstd),
-                           L.ptr(gamma), L.ptr(beta), G, cout, 1, L.ptr(out), L.ptr(arg), L.ptr(ysel))
-                    ys.append(ysel)  # stands in for y_L in the saved list: (G, cout), the pre-BN value behind each pooled output
-                    means.append(mean)
-                    invstds.append(invstd)
-                    break
-                y = torch.empty((R, cout), dtype=torch.float32, device=dev)
-                if training and R > 0:
-                    # forward + batch statistics + BatchNorm finalize (mean / invstd / running statistics) in one call: the finalize
-                    # rides on the last workgroup of the statistics reduction
-                    rm, rv, nbt = bn_buffers[i]
-                    mean = torch.empty(cout, dtype=torch.float32, device=dev)
-                    invstd = torch.empty(cout, dtype=torch.float32, device=dev)
-                    L.call('mvp_mlp_forward_bn_f32', x, L.ptr(x), R, cin, x.size(1), L.ptr(w), cin, cout, L.ptr(act[0]), L.ptr(act[1]),
-                           L.ptr(act[2]), L.ptr(act[3]), L.ptr(y), L.ptr(stat), L.ptr(_partial(R, cout, dev)), float(eps), float(mom),
-                           L.ptr(mean), L.ptr(invstd), L.ptr(rm), L.ptr(rv), L.ptr(nbt), prec=prec)
-                    ys.append(y)
-                    means.append(mean)
-                    invstds.append(invstd)
-                    act = (mean, invstd, gamma, beta)
-                    x = y
-                    continue
-                L.call('mvp_mlp_forward_f32', x, L.ptr(x), R, cin, x.size(1), L.ptr(w), cin, cout, L.ptr(act[0]), L.ptr(act[1]),
-                       L.ptr(act[2]), L.ptr(act[3]), None, L.ptr(y), L.ptr(stat), L.ptr(_partial(R, cout, dev) if training else None), prec=prec)
-            rm, rv, nbt = bn_buffers[i]
-            if training:
-                mean = torch.empty(cout, dtype=torch.float32, device=dev)
-                invstd = torch.empty(cout, dtype=torch.float32, device=dev)
-                L.call('mvp_bn_finalize_f32', y, L.ptr(stat), R, cout, float(eps), float(mom), L.ptr(mean), L.ptr(invstd),
-                       L.ptr(rm), L.ptr(rv), L.ptr(nbt))
-            else:
-                mean, invstd = rm, eval_invstd.get(rv, eps)
+                y, mean, invstd = _fwd_layer(x, w, act, training, stat, bn_buffers[i], eps, mom, prec)
             ys.append(y)
             means.append(mean)
             invstds.append(invstd)
-            act = (mean, invstd, gamma, beta)
-            x = y
+            x, act = y, (L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta))
         cl = ys[-1].size(1)
         G = R // K
         if not pooled and drop_p > 0:
@@ -1038,263 +1261,43 @@ class MLPChainRows(torch.autograd.Function):
         saved = ctx.saved_tensors
         x0, out, arg = saved[0], saved[1], saved[2]
         ys = saved[3:3 + nl]
-        means = saved[3 + nl:3 + 2 * nl]
-        invstds = saved[3 + 2 * nl:3 + 3 * nl]
         params = list(saved[3 + 3 * nl:])
         if not ctx.first_linear:
             params.insert(0, None)
         grads = [None] * (3 * nl)
         g = grad_out.contiguous()
-        G = R // K
-        # last layer: through max-over-K + ReLU + BN
-        cl = ys[-1].size(1)
-        pool = None
-        wl = params[3 * (nl - 1)]
-        # the consumer of this chain's output already applied the ReLU mask and summed the columns (ActivationHandOver): g IS dz_L
-        handed = None
-        if ctx.act_out is not None and ctx.act_out.stat is not None:
-            handed, ctx.act_out.stat = ctx.act_out.stat, None
-        last_wide = bool(handed is None and not ctx.pooled and K == 1 and nl >= 2 and wl is not None and g.is_cuda and
-                         wide_backward_ok(ctx.prec, R, wl.size(0), wl.size(1), ys[nl - 2].size(1)) and R * cl < 2 ** 32 and
-                         aligned16(g, ys[-1], ys[nl - 2]))
-        # ... and the last layer in front of a SUM over K (FeatureAggregation, arg is None): the same one-pass backward takes the gradient of the
-        # POOLED output and reads row r / K of it (mvp_mlp_layer_backward_wide_pooled_p_f32): no (R, C) gradient tensor, no pass that writes it
-        last_wide_sum = bool(WIDE_BWD_POOLED and not ctx.pooled and K > 1 and arg is None and ctx.dropout[0] == 0 and nl >= 2 and wl is not None and
-                             g.is_cuda and wide_backward_ok(ctx.prec, R, wl.size(0), wl.size(1), ys[nl - 2].size(1)) and R * cl < 2 ** 32 and
-                             aligned16(g, ys[-1], ys[nl - 2]))
-        if handed is not None:
-            dy, dgam, dbet = None, None, None
-        elif ctx.pooled:
-            # the last layer's (R, cl) output does not exist: its BatchNorm-backward column sums come from the (G, cl) tensors, dy_L is
-            # formed inside the one-kernel layer backward from the re-computed y_L
-            ysel = ys[-1]
-            stat_l = torch.empty(2 * cl, dtype=torch.float64, device=g.device)
-            L.call('mvp_pool_backward_stats_f32', g, L.ptr(g), L.ptr(out), L.ptr(ysel), L.ptr(means[-1]), L.ptr(invstds[-1]), G, cl, 1,
-                   L.ptr(stat_l), L.ptr(_cs_partial(G, cl, g.device)))
-            pool = (g, out, arg)
-            dy, dgam, dbet = None, None, None
-        elif last_wide_sum:
-            stat_d = torch.empty(2 * cl, dtype=torch.float64, device=g.device)
-            L.call('mvp_bn_rows_backward_f32', g, L.ptr(g), None, None, L.ptr(ys[-1]), L.ptr(means[-1]), L.ptr(invstds[-1]), L.ptr(params[-2]),
-                   L.ptr(params[-1]), G, K, cl, 1, int(training), L.ptr(stat_d), None, None, None, L.ptr(_cs_partial(R, cl, g.device)))
-            dy, dgam, dbet = None, None, None
-        elif last_wide:
-            # the last layer goes through the one-pass wide backward (mode 2): only the two column sums of dz_L = g * keep * relu'(bn(y_L)) are
-            # computed here; the finish, the masks and dy_L happen while that kernel loads its rows (no dy_L tensor, no finish pass)
-            stat_d = torch.empty(2 * cl, dtype=torch.float64, device=g.device)
-            L.call('mvp_bn_rows_backward_dropout_f32', g, L.ptr(g), L.ptr(ys[-1]), L.ptr(means[-1]), L.ptr(invstds[-1]), L.ptr(params[-2]),
-                   L.ptr(params[-1]), R, cl, 1, int(training), L.ptr(stat_d), None, None, None, L.ptr(_cs_partial(R, cl, g.device)),
-                   ctx.dropout[0], ctx.dropout[1])
-            dy, dgam, dbet = None, None, None
-        elif ctx.dropout[0] > 0:  # the keep mask is regenerated from (p, seed) inside the BatchNorm-backward passes
-            stat_d = torch.empty(2 * cl, dtype=torch.float64, device=g.device)
-            dy = torch.empty_like(ys[-1])
-            dgb = torch.empty((2, cl), dtype=torch.float32, device=g.device)
-            L.call('mvp_bn_rows_backward_dropout_f32', g, L.ptr(g), L.ptr(ys[-1]), L.ptr(means[-1]), L.ptr(invstds[-1]), L.ptr(params[-2]),
-                   L.ptr(params[-1]), R, cl, 1, int(training), L.ptr(stat_d), L.ptr(dy), L.ptr(dgb[0]), L.ptr(dgb[1]),
-                   L.ptr(_cs_partial(R, cl, g.device)), ctx.dropout[0], ctx.dropout[1])
-            dgam, dbet = dgb[0], dgb[1]
-        else:
-            dy, dgam, dbet = _bn_backward(g, out, arg, ys[-1], means[-1], invstds[-1], params[-2], params[-1], G, K, cl, True, training)
-        dx0 = None
-        none4 = (None, None, None, None)
-        # `dW` and `stat` are accumulated into by the kernels: two zeroed arenas for the whole chain
-        w_numel = [0 if params[3 * i] is None else params[3 * i].numel() for i in range(nl)]
-        dw_arena = zero_pool.zeros(sum(w_numel), torch.float32, g.device)
-        st_arena = zero_pool.zeros(2 * sum(params[3 * i].size(1) for i in range(1, nl)), torch.float64, g.device)
-        dw_off, st_off = 0, 0
-        dev = g.device
-        split = ctx.prec[0] != 0   # the one-kernel layer backward (mvp_mlp_layer_backward_f32) contracts in split-bf16 only
-        # State while walking the layers backwards: `gcur` is either dy_i itself (pending is None) or dz_i = the gradient w.r.t.
-        # layer i's ACTIVATION already masked by its ReLU, with `pending` = its two BatchNorm-backward column sums: the "finish"
-        # step (dz_i -> dy_i) then happens INSIDE the fused layer kernel, or as its own pass when the layer cannot be fused.
-        gcur, pending = dy, None
-        if handed is not None:
-            gcur, pending = g, handed
-        elif pool is not None:
-            gcur, pending = None, stat_l
-        elif last_wide or last_wide_sum:
-            gcur, pending = g, stat_d
-        dw_aside = bool(DW_SIDE_STREAM and ctx.dw_use is not None and ctx.dw_use.aside_ok())
+        wk = _ChainWalk(ctx, ys, saved[3 + nl:3 + 2 * nl], saved[3 + 2 * nl:3 + 3 * nl], params, g.device)
+        gcur, pending, grads[-2], grads[-1] = wk.head(g, out, arg)
+        prec, reproducible, need_dx0 = ctx.prec, L.DW_WORKSPACE, ctx.needs_input_grad[0]
+        defer_open = ctx.defer is not None and ctx.defer.accepts and ctx.defer.info is None
         for i in range(nl - 1, -1, -1):
             w = params[3 * i]
-            cout = ys[i].size(1)
-            need_dz = (i > 0 or ctx.needs_input_grad[0]) and w is not None
-            cin = 0 if w is None else w.size(1)
             src = None if w is None else (x0 if i == 0 else ys[i - 1])
-            pool_here = pool is not None and i == nl - 1
-            rel, w0_param = ctx.rel if i == 0 else (None, None)
-            wide = bool(i > 0 and w is not None and not pool_here and rel is None and need_dz and wide_backward_ok(ctx.prec, R, cout, cin, src.size(1)) and
-                        aligned16(gcur, ys[i], src))
-            fuse = wide or pool_here or (split and w is not None and cout <= FUSE_BWD_MAX_COUT and cin <= FUSE_BWD_MAX_CIN and rel is None and
-                                         (not need_dz or cin % 4 == 0) and (i > 0 or src.size(1) == cin or not need_dz))
-            dxw = bool(not fuse and i > 0 and w is not None and rel is None and need_dz and not L.DW_WORKSPACE and
-                       dx_wide_ok(ctx.prec, R, cout, cin, src.size(1), pending is not None) and aligned16(gcur, ys[i], src) and w.is_contiguous())
-            assert wide or not ((last_wide or last_wide_sum) and i == nl - 1)
-            if pending is not None and w is None and ctx.defer is not None and ctx.defer.accepts and ctx.defer.info is None:
-                # i == 0, x0 was this layer's pre-BN output and its ONLY consumer gathers it (DeferredFinish): dz_0 goes back unfinished, the
-                # gather forms dy_0 on load.  The BatchNorm parameter gradients are the two column sums themselves.
-                ctx.defer.info = (ys[0], means[0], invstds[0], params[1], pending, training)
-                dgb = pending.view(2, cout).to(torch.float32)
-                grads[1], grads[2] = dgb[1], dgb[0]
-                dx0 = gcur
-                break
-            if (pending is not None and not fuse and DW_FINISH_ON_LOAD and i == 0 and rel is not None and not need_dz and ctx.prec[0] != 0 and
-                    ctx.prec[1] in (1, 3) and cout % 4 == 0 and cout > 32 and src.size(1) > 32 and src.size(1) == w.size(1) - 4 and
-                    aligned16(gcur, ys[0]) and max(cout, src.size(1)) >= L.mlp_min_width()):
-                # FIRST layer over [x0 | rel] whose input needs no gradient (FeatureAggregation on a frozen 2D branch): dy_0 is needed by the two
-                # weight-gradient launches only, and they form it from (dz_0, y_0) while they load it (mvp_mlp_weight_grad_finish_p_f32): no finish
-                # pass (95 us at the very end of the training stream, where nothing overlaps it), no (R, C) dy tensor.  The BatchNorm parameter
-                # gradients are the two column sums.
-                cin_f = src.size(1)
-                dw = dw_arena[dw_off:dw_off + cout * cin].view(cout, cin)
-                dw_off += cout * cin
-                grads[0] = dw
-                dgb0 = pending.view(2, cout).to(torch.float32)
-                grads[1], grads[2] = dgb0[1], dgb0[0]
-                ws_ptr, ws_floats = L.current_dw_workspace(dev)
-                if REL_DW_FUSED and ws_ptr is None and 32 < cin_f <= 64 and aligned16(src, rel):
-                    # ... and both column groups from ONE launch (mvp_mlp_weight_grad_finish_rel_p_f32: the relation columns as a third operand block):
-                    # the two launches below each stream dz_0 and y_0 -- 1.0 GB for what is 0.6 GB, HBM-bound, with nothing left to overlap them.
-                    # On the calling stream: nothing else is queued behind it.
-                    L.call('mvp_mlp_weight_grad_finish_rel_p_f32', gcur, L.ptr(gcur), L.ptr(ys[0]), L.ptr(means[0]), L.ptr(invstds[0]), L.ptr(params[1]),
-                           L.ptr(pending), int(training), L.ptr(src), R, cout, cin_f, cin_f, L.ptr(rel), L.ptr(dw), L.ptr_at(dw, cin_f), cin, *ctx.prec)
-                    break
-                for xs, ncol, c0 in ((src, cin_f, 0), (rel, 4, cin_f)):
-                    fargs = (L.ptr(gcur), L.ptr(ys[0]), L.ptr(means[0]), L.ptr(invstds[0]), L.ptr(params[1]), L.ptr(pending), int(training), L.ptr(xs), R,
-                             cout, ncol, ncol, L.ptr_at(dw, c0), cin)
-                    if dw_aside and xs is not rel and ws_ptr is None:
-                        # (everything the side-stream kernel reads stays alive until the join -- also the statistics and gamma, which this node's saved
-                        # tensors would otherwise release to the calling stream's allocator when the node is freed: ADVICE r5)
-                        side_stream.run(dev, 'mvp_mlp_weight_grad_finish_p_f32', fargs + (None, 0) + tuple(ctx.prec),
-                                        (gcur, ys[0], xs, dw, pending, means[0], invstds[0], params[1]))
-                    else:
-                        L.call('mvp_mlp_weight_grad_finish_p_f32', gcur, *(fargs + (ws_ptr, ws_floats) + tuple(ctx.prec)))
-                break
-            if pending is not None and not fuse and not dxw:
-                # dz_i -> dy_i as its own pass (also hands back the BatchNorm parameter gradients)
-                dyi = torch.empty((R, cout), dtype=torch.float32, device=dev)
-                dgb = torch.empty((2, cout), dtype=torch.float32, device=dev)
-                L.call('mvp_bn_rows_backward_finish_f32', gcur, L.ptr(gcur), L.ptr(ys[i]), L.ptr(means[i]), L.ptr(invstds[i]), L.ptr(params[3 * i + 1]),
-                       L.ptr(params[3 * i + 2]), R, cout, int(training), L.ptr(pending), L.ptr(dyi), L.ptr(dgb[0]), L.ptr(dgb[1]))
-                gcur, pending = dyi, None
-                dgam, dbet = dgb[0], dgb[1]
-            if pending is None:
-                grads[3 * i + 1], grads[3 * i + 2] = dgam, dbet
-            if dxw:
-                # a 256- / 512-wide inner layer: input gradient in one pass (finish of dz_i on load when it is pending, ReLU mask + column sums of
-                # layer i - 1 in the epilogue), the weight gradient beside the chain with the same finish on load -- no finish pass, no dy_i tensor
-                act = (means[i - 1], invstds[i - 1], params[3 * i - 2], params[3 * i - 1])
-                dw = dw_arena[dw_off:dw_off + cout * cin].view(cout, cin)
-                dw_off += cout * cin
-                grads[3 * i] = dw
-                stat = st_arena[st_off:st_off + 2 * cin]
-                st_off += 2 * cin
-                dz = torch.empty((R, cin), dtype=torch.float32, device=dev)
-                fin = pending is not None
-                dgb = torch.empty((2, cout), dtype=torch.float32, device=dev) if fin else None
-                if fin:
-                    wg_name = 'mvp_mlp_weight_grad_finish_act_p_f32'
-                    wg_args = (L.ptr(gcur), L.ptr(ys[i]), L.ptr(means[i]), L.ptr(invstds[i]), L.ptr(params[3 * i + 1]), L.ptr(pending), int(training), L.ptr(src),
-                               R, cout, cin, src.size(1), L.ptr(act[0]), L.ptr(act[1]), L.ptr(act[2]), L.ptr(act[3]), L.ptr(dw), cin, None, 0) + tuple(ctx.prec)
-                    wg_keep = (gcur, ys[i], means[i], invstds[i], params[3 * i + 1], pending, src, dw) + act
-                    if dw_aside:
-                        side_stream.run(dev, wg_name, wg_args, wg_keep)
-                    else:
-                        L.call(wg_name, gcur, *wg_args)
-                else:
-                    wg_args = (L.ptr(gcur), L.ptr(src), R, cout, cin, src.size(1), L.ptr(act[0]), L.ptr(act[1]), L.ptr(act[2]), L.ptr(act[3]), L.ptr(dw), cin)
-                    if dw_aside:
-                        side_stream.run(dev, 'mvp_mlp_weight_grad_f32', wg_args, (gcur, src, dw) + act, prec=ctx.prec)
-                    else:
-                        L.call('mvp_mlp_weight_grad_f32', gcur, *wg_args, prec=ctx.prec)
-                nbytes = int(L.lib().mvp_mlp_input_grad_wide_workspace_bytes(cout, cin))
-                wimg = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                L.call('mvp_mlp_input_grad_wide_f32', gcur, L.ptr(gcur), L.ptr(ys[i]) if fin else None, L.ptr(means[i]) if fin else None,
-                       L.ptr(invstds[i]) if fin else None, L.ptr(params[3 * i + 1]) if fin else None, L.ptr(pending), L.ptr(None if dgb is None else dgb[0]),
-                       L.ptr(None if dgb is None else dgb[1]), int(training), L.ptr(src), src.size(1), L.ptr(act[0]), L.ptr(act[1]), L.ptr(act[2]), L.ptr(act[3]),
-                       L.ptr(w), cin, R, cout, cin, L.ptr(dz), L.ptr(stat), L.ptr(wimg), nbytes, prec=ctx.prec)
-                if fin:
-                    grads[3 * i + 1], grads[3 * i + 2] = dgb[0], dgb[1]
-                gcur, pending = dz, stat
-                continue
-            if w is None:  # i == 0: x0 was this layer's pre-BN output, its gradient is dy itself
-                dx0 = gcur
-                break
-            act = none4 if i == 0 else (means[i - 1], invstds[i - 1], params[3 * i - 2], params[3 * i - 1])
-            dw = dw_arena[dw_off:dw_off + cout * cin].view(cout, cin)
-            dw_off += cout * cin
-            grads[3 * i] = dw
-            stat = None
-            if i > 0:
-                stat = st_arena[st_off:st_off + 2 * cin]
-                st_off += 2 * cin
-            dz = torch.empty((R, cin if rel is None else src.size(1)), dtype=torch.float32, device=dev) if need_dz else None
-            if rel is not None:
-                # first layer over [x0 | rel]: the feature columns and the four relation columns of dW from two launches (beside the chain
-                # when allowed), the input gradient (only when x0 needs one) from the feature columns of the weight
-                cin_f = src.size(1)
-                for xs, ncol, c0 in ((src, cin_f, 0), (rel, 4, cin_f)):
-                    wg_args = (L.ptr(gcur), L.ptr(xs), R, cout, ncol, ncol, None, None, None, None, L.ptr_at(dw, c0), cin)
-                    # this is the END of the backward pass when x0 needs no gradient (FeatureAggregation on a frozen 2D branch): nothing is left
-                    # for the calling stream to do, so only the feature columns go beside it and the four relation columns run ON it -- the
-                    # two launches (each streams dy_1 once) overlap instead of queueing on the one side stream (REL_DW_SPLIT: A/B switch)
-                    if dw_aside and not (REL_DW_SPLIT and xs is rel and not need_dz):
-                        side_stream.run(dev, 'mvp_mlp_weight_grad_f32', wg_args, (gcur, xs, dw), prec=ctx.prec)
-                    else:
-                        L.call('mvp_mlp_weight_grad_f32', gcur, *wg_args, prec=ctx.prec)
-                if need_dz:
-                    wf = weight_slices.get(w0_param, 0, cin_f, cin_f)
-                    L.call('mvp_mlp_input_grad_f32', gcur, L.ptr(gcur), R, cout, L.ptr(wf), cin_f, None, None, None, None, None, L.ptr(dz), None, None, prec=ctx.prec)
-                    dx0 = dz
-                break
-            if wide:
-                # mode 0: gcur is dy_i; 1: dz_i (finish inside); 2: the gradient of the layer's (dropped-out) activation (last layer)
-                mode = 0 if pending is None else (2 if ((last_wide or last_wide_sum) and i == nl - 1) else 1)
-                pool_k = K if (last_wide_sum and i == nl - 1) else 1
-                dgb = torch.empty((2, cout), dtype=torch.float32, device=dev) if pending is not None else None
-                ticket = zero_pool.zeros(2, torch.int32, dev)
-                ws_ptr, ws_floats = L.current_dw_workspace(dev)
-                fin = pending is not None
-                L.call('mvp_mlp_layer_backward_wide_pooled_f32', src, L.ptr(gcur), L.ptr(ys[i]) if fin else None, L.ptr(means[i]) if fin else None,
-                       L.ptr(invstds[i]) if fin else None, L.ptr(params[3 * i + 1]) if fin else None, L.ptr(params[3 * i + 2]) if mode == 2 else None,
-                       L.ptr(pending), L.ptr(None if dgb is None else dgb[0]), L.ptr(None if dgb is None else dgb[1]), int(training), mode, pool_k,
-                       float(ctx.dropout[0]) if mode == 2 else 0.0, int(ctx.dropout[1]) if mode == 2 else 0, L.ptr(src), src.size(1), L.ptr(act[0]),
-                       L.ptr(act[1]), L.ptr(act[2]), L.ptr(act[3]), L.ptr(w), cin, R, cout, cin, L.ptr(dw), cin, L.ptr(dz), L.ptr(stat), L.ptr(ticket),
-                       ws_ptr, ws_floats, prec=ctx.prec)
-                if pending is not None:
-                    grads[3 * i + 1], grads[3 * i + 2] = dgb[0], dgb[1]
-            elif fuse:
-                dgb = torch.empty((2, cout), dtype=torch.float32, device=dev) if pending is not None else None
-                part = torch.empty(L.lib().mvp_mlp_layer_backward_partial_count(R, cin), dtype=torch.float64, device=dev) if (i > 0 and need_dz) else None
-                L.call('mvp_mlp_layer_backward_f32', src, L.ptr(gcur), L.ptr(ys[i]) if (pending is not None and not pool_here) else None,
-                       L.ptr(means[i]) if pending is not None else None, L.ptr(invstds[i]) if pending is not None else None,
-                       L.ptr(params[3 * i + 1]) if pending is not None else None, L.ptr(pending), L.ptr(None if dgb is None else dgb[0]),
-                       L.ptr(None if dgb is None else dgb[1]), int(training), L.ptr(src), src.size(1), L.ptr(act[0]), L.ptr(act[1]), L.ptr(act[2]),
-                       L.ptr(act[3]), L.ptr(w), cin, R, cout, cin, L.ptr(dw), cin, L.ptr(dz), L.ptr(stat), L.ptr(part),
-                       L.ptr(pool[0]) if pool_here else None, L.ptr(pool[1]) if pool_here else None, L.ptr(pool[2]) if pool_here else None, prec=ctx.prec)
-                if pending is not None:
-                    grads[3 * i + 1], grads[3 * i + 2] = dgb[0], dgb[1]
+            need_dz = (i > 0 or need_dx0) and w is not None
+            last = i == nl - 1
+            route = _backward_route(prec, reproducible, R, i, w, ys[i], src, gcur, pending, ctx.rel[0] if i == 0 else None, need_dz,
+                                    last and wk.pool is not None, defer_open, last and wk.last_wide)
+            if pending is not None and route in ('tile', 'rel', 'given'):
+                gcur, grads[3 * i + 1], grads[3 * i + 2] = wk.finish(i, gcur, pending)
+                pending = None
+            if route == 'wide':
+                step = wk.wide(i, gcur, pending, w, src)
+            elif route == 'fuse':
+                step = wk.fuse(i, gcur, pending, w, src, need_dz)
+            elif route == 'tile':
+                step = wk.tile(i, gcur, w, src, need_dz)
+            elif route == 'dxw':
+                step = wk.dxw(i, gcur, pending, w, src)
+            elif w is not None:
+                step = wk.rel(gcur, pending, w, src, need_dz, route)
             else:
-                wg_args = (L.ptr(gcur), L.ptr(src), R, cout, cin, src.size(1), L.ptr(act[0]), L.ptr(act[1]), L.ptr(act[2]), L.ptr(act[3]),
-                           L.ptr(dw), cin)
-                if _EXP_SKIP_DW:
-                    pass  # (timing experiment only: tools/exp/README.md, "what the graph step would cost with the weight gradients for free")
-                elif dw_aside:
-                    side_stream.run(dev, 'mvp_mlp_weight_grad_f32', wg_args, (gcur, src, dw) + tuple(t for t in act if t is not None), prec=ctx.prec)
-                else:
-                    L.call('mvp_mlp_weight_grad_f32', gcur, *wg_args, prec=ctx.prec)
-                if need_dz and i > 0:
-                    # d(input) = dy . W with the previous layer's ReLU mask and BN-backward column sums in the epilogue
-                    pm, pi, pg, pb = act
-                    L.call('mvp_mlp_input_grad_f32', gcur, L.ptr(gcur), R, cout, L.ptr(w), cin, L.ptr(ys[i - 1]), L.ptr(pm), L.ptr(pi),
-                           L.ptr(pg), L.ptr(pb), L.ptr(dz), L.ptr(stat), L.ptr(_partial(R, cin, dev)), prec=ctx.prec)
-                elif need_dz:
-                    L.call('mvp_mlp_input_grad_f32', gcur, L.ptr(gcur), R, cout, L.ptr(w), cin, None, None, None, None, None, L.ptr(dz), None, None, prec=ctx.prec)
-            if i > 0:
-                gcur, pending = dz, stat
-            elif need_dz:
-                dx0 = dz if x0.size(1) == cin else F.pad(dz, (0, x0.size(1) - cin))
+                step = wk.defer(gcur, pending, ctx.defer) if route == 'defer' else (gcur, None, None, None, None)  # (given: dy_0 is the input's gradient)
+            gcur, pending, grads[3 * i], dgam, dbet = step
+            if dgam is not None:
+                grads[3 * i + 1], grads[3 * i + 2] = dgam, dbet
+        dx0 = gcur  # (after layer 0: the input's gradient, or None)
+        if dx0 is not None and dx0.size(1) != x0.size(1):
+            dx0 = F.pad(dx0, (0, x0.size(1) - dx0.size(1)))
         if ctx.dw_use is not None:
             ctx.dw_use.done = True
         return (dx0, None, None, None, None, None, None) + tuple(grads)
@@ -1400,12 +1403,9 @@ class LinearRows(torch.autograd.Function):
                 wg_args = (L.ptr(gy), L.ptr(x), R, cout, ncol, cin, None, None, None, None, L.ptr_at(gw, c0), gw.numel() // cout)
                 use = ctx.dw_use
                 aside = use is not None and DW_SIDE_STREAM and use.aside_ok()
-                if aside:
-                    # (gw itself must not be kept: AccumulateGrad takes a gradient over as it is only while nobody else holds the tensor --
-                    # otherwise it CLONES it on the calling stream, before the side stream has written it; the parameter's .grad keeps the memory)
-                    side_stream.run(gy.device, 'mvp_mlp_weight_grad_f32', wg_args, (gy, x), prec=ctx.prec)
-                else:
-                    L.call('mvp_mlp_weight_grad_f32', gy, *wg_args, prec=ctx.prec)
+                # (gw itself must not be kept: AccumulateGrad takes a gradient over as it is only while nobody else holds the tensor --
+                # otherwise it CLONES it on the calling stream, before the side stream has written it; the parameter's .grad keeps the memory)
+                _weight_grad(aside, gy.device, 'mvp_mlp_weight_grad_f32', wg_args, (gy, x), ctx.prec)
                 if use is not None:
                     use.done = True
         if ctx.has_bias and ctx.needs_input_grad[2]:
