@@ -283,6 +283,32 @@ int mvp_lift_aug_f32(const void* depth, int depth_is_u16, const float* kinv, con
  * / `image_xyz` (scannet_2d3d.py:400-409) for tensors that did not go through mvp_lift_aug_f32.  In place allowed. */
 int mvp_rotate_rows_f32(const float* xyz, const double* rot, int64_t B, int64_t R, float* out, mvp_stream_t stream);
 
+/* ---- frame selection inputs (NEW on the device; the reference computes the overlap offline) ----
+ * RGB-D overlap: replaces compute_rgbd_knn (mvpnet/data/preprocess/preprocess.py:99-170: un-project every frame, look up each
+ * pixel's nearest base point in an open3d KD-tree, max_nn = 1, mark it when closer than 0.1 m).
+ *   depth (F,h,w) metres float32 or millimetres uint16; kinv (F,3,3), pose (F,4,4) float32; base_points (nb,3) float32
+ *   -> overlap_bits (F,W) uint32, W = ceil(nb / 32), zero-filled here: bit j % 32 of word j / 32 of row f = frame f sees base point j.
+ * Pinned definition:
+ *   - a pixel's world point is what mvp_unproject_* writes for it with box = NULL, and it takes part when that mask is set (z_cam > 0);
+ *   - a frame with a non-finite entry in its 4x4 pose is skipped, its row stays zero (preprocess.py:137-139);
+ *   - j* = argmin_j d2, d2 = (dx*dx + dy*dy) + dz*dz in float32 without contraction (the arithmetic of the ball query), lowest j on ties;
+ *   - bit (f, j*) is set iff d2 < fl32(fl32(radius) * fl32(radius)); only the nearest point is marked (preprocess.py:156).
+ * The base points are held in LDS: nb <= MVP_OVERLAP_MAX_BASE, MVP_EUNSUPPORTED beyond.  F * h * w < 2^31, radius >= 0. */
+#define MVP_OVERLAP_MAX_BASE 4096
+int mvp_frame_overlap_f32(const float* depth_m, const float* kinv, const float* pose, const float* base_points, int64_t F, int64_t h,
+                          int64_t w, int64_t nb, float radius, uint32_t* overlap_bits, mvp_stream_t stream);
+int mvp_frame_overlap_u16(const uint16_t* depth_mm, const float* kinv, const float* pose, const float* base_points, int64_t F, int64_t h,
+                          int64_t w, int64_t nb, float radius, uint32_t* overlap_bits, mvp_stream_t stream);
+
+/* greedy frame selection for all chunks of a scene in one launch: per chunk c the result of
+ * select_frames(pointwise_rgbd_overlap[base points of the chunk], n_pick) (mvpnet/data/scannet_2d3d.py:20-30, called from :204-220).
+ *   overlap_bits (F,W) as above; chunk_bits (C,W): bit j of row c = base point j lies in chunk c
+ *   -> picked (C,n_pick) int64 frame indices; gain (C,n_pick) int32 or NULL: base points of the chunk newly covered by each pick.
+ * Each pick takes the frame covering most still-uncovered base points of the chunk, the LOWEST frame index on ties (numpy.argmax) --
+ * frame 0 again and again once nothing is left to cover.  F >= 1; W <= 1024 (32768 base points), MVP_EUNSUPPORTED beyond. */
+int mvp_select_frames_u32(const uint32_t* overlap_bits, const uint32_t* chunk_bits, int64_t F, int64_t C, int64_t W, int64_t n_pick,
+                          int64_t* picked, int32_t* gain, mvp_stream_t stream);
+
 /* Column slices of several row-major float matrices in one launch (host-side helper of the shared-MLP path: the reference slices
  * nothing -- it concatenates the inputs instead, modules.py:32-35,178-186 -- the linear-first factorisation of those layers needs
  * each column group of the weight as its own aligned operand).  table: n x 6 int64 ON THE DEVICE, per entry

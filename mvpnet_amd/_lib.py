@@ -132,6 +132,9 @@ _SIGNATURES = {
     'mvp_seg_loss_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr],
     'mvp_seg_loss_backward_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     'mvp_seg_confusion_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr],
+    'mvp_frame_overlap_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _ptr, _ptr],
+    'mvp_frame_overlap_u16': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _ptr, _ptr],
+    'mvp_select_frames_u32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
 }
 # the shared-MLP entry points with the precision as arguments (csrc/mlp_prec.hip): base parameters + (precision, precision_backward)
 for _n in ['mvp_mlp_forward_f32', 'mvp_mlp_forward_bn_f32', 'mvp_mlp_forward_rel_bn_f32', 'mvp_mlp_forward_pool_f32', 'mvp_mlp_input_grad_f32', 'mvp_mlp_input_grad_dropout_f32',

@@ -67,3 +67,36 @@ def crop_pad_choice(n, nb_pts, generator=None, device=None):
         pad = torch.randint(n, (nb_pts - n,), generator=generator, device=device)
         return torch.cat([torch.arange(n, device=device), pad])
     return torch.randperm(n, generator=generator, device=device)[:nb_pts]
+
+
+def _kinv_of(cam_matrix):
+    """inverse of the 3x3 intrinsics in float32 on the host, as the loader does it (np.linalg.inv(cam_matrix[:3, :3]), scannet_2d3d.py:38)."""
+    cam = cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)
+    return np.linalg.inv(cam.astype(np.float32)[..., :3, :3])
+
+
+def compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=2000, radius=0.1, generator=None):
+    """`compute_rgbd_knn` (mvpnet/data/preprocess/preprocess.py:99-170) on the device: the two arrays the reference stores per scene.
+    points (n,3) float32 device tensor (the whole scene), depth (F,h,w) float32 metres or (u)int16 millimetres, cam_matrix (3,3) or
+    (4,4) intrinsics OF THE DEPTH MAPS' RESOLUTION (array or tensor; (F,3,3) for per-frame intrinsics), pose (F,4,4) float32.
+    -> base_point_ind (num_base_pts,) int64, overlaps (num_base_pts, F) bool  (`base_point_ind`, `pointwise_rgbd_overlap`).
+
+    Base points are `randperm(n)[:num_base_pts]` from `generator` (or torch's global generator of the device): the same LAW as the
+    reference's `np.random.choice(n, num_base_pts, replace=False)`, not the same draws.
+    The reference works on 80x60 maps made from the 640x480 depth PNGs by PIL's NEAREST resize, which for a factor of 8 samples the
+    centre of every 8x8 block, and divides the first two rows of the intrinsics by 8 (preprocess.py:120-126, :143-145); a caller
+    holding full-size maps gets the same input with `depth[:, 4::8, 4::8]` and `cam_matrix[0] /= 8; cam_matrix[1] /= 8`.
+    The nearest-neighbour rule is pinned in include/mvp_hip.h (float32, strict `<`); ops.rgbd_overlap is the kernel's wrapper."""
+    from . import ops
+    assert points.dim() == 2 and points.size(1) == 3 and points.dtype == torch.float32
+    n = points.size(0)
+    if num_base_pts > n:
+        raise ValueError('cannot take {} base points from a scene of {} points'.format(num_base_pts, n))
+    F = depth.size(0)
+    base_point_ind = torch.randperm(n, generator=generator, device=points.device if generator is None else generator.device)
+    base_point_ind = base_point_ind[:num_base_pts].to(points.device)
+    kinv = torch.from_numpy(np.ascontiguousarray(_kinv_of(cam_matrix))).to(points.device)
+    if kinv.dim() == 2:
+        kinv = kinv.expand(F, 3, 3)
+    overlaps = ops.rgbd_overlap(depth.contiguous(), kinv.contiguous(), pose.contiguous(), points[base_point_ind].contiguous(), radius=radius)
+    return base_point_ind, overlaps

@@ -14,6 +14,7 @@
 // XCD-aware placement (workgroup L runs on XCD L % 8, observed, used for speed only) keeps each chunk's 0.9 MB of records in ONE
 // XCD's private 4 MB L2.
 #include "pixel_knn_core.h"
+#include "unproject_core.h"
 #include <stdlib.h>
 
 namespace {
@@ -55,26 +56,11 @@ __global__ __launch_bounds__(kPrepThreads) void lift_prepare_kernel(const DepthT
     *pl = (uint16_t)kPlaneInvalid;
     return;
   }
-  const float* Ki = kinv + (size_t)bv * 9;
-  const float* Pm = pose + (size_t)bv * 16;
-  const double k0 = Ki[0], k1 = Ki[1], k2 = Ki[2], k3 = Ki[3], k4 = Ki[4], k5 = Ki[5], k6 = Ki[6], k7 = Ki[7], k8 = Ki[8];
-  const double p0 = Pm[0], p1 = Pm[1], p2 = Pm[2], p3 = Pm[3], p4 = Pm[4], p5 = Pm[5], p6 = Pm[6], p7 = Pm[7], p8 = Pm[8],
-               p9 = Pm[9], p10 = Pm[10], p11 = Pm[11];
+  const UnprojectCam cm = unproject_cam(kinv + (size_t)bv * 9, pose + (size_t)bv * 16);
   const size_t p = (size_t)bv * h * w + (size_t)v * w + u;
-  float df;
-  if constexpr (sizeof(DepthT) == 2)
-    df = __fdiv_rn((float)depth[p], 1000.0f);
-  else
-    df = depth[p];
-  // identical arithmetic to unproject_kernel (lifting.hip): float64, one rounding to float32
-  const double d = (double)df, du = (double)u, dv = (double)v;
-  const double rx = (k0 * du + k1 * dv) + k2;
-  const double ry = (k3 * du + k4 * dv) + k5;
-  const double rz = (k6 * du + k7 * dv) + k8;
-  const double xc = rx * d, yc = ry * d, zc = rz * d;
-  const double xw = ((xc * p0 + yc * p1) + zc * p2) + p3;
-  const double yw = ((xc * p4 + yc * p5) + zc * p6) + p7;
-  const double zw = ((xc * p8 + yc * p9) + zc * p10) + p11;
+  // the arithmetic of unproject_kernel (lifting.hip), shared through unproject_core.h: float64, one rounding to float32
+  double xw, yw, zw, zc;
+  unproject_pixel(cm, depth_metres(depth, p), u, v, xw, yw, zw, zc);
   bool ok = zc > 0.0;
   if (box) {
     const float* bx = box + (size_t)(bv / nv) * 4;

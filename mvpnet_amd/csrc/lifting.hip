@@ -7,6 +7,7 @@
 // ((B,nv,h,w,C): one 4*C-byte contiguous row per pixel), so a gathered neighbour is one
 // coalesced row read instead of C scattered words.
 #include "common.h"
+#include "unproject_core.h"
 
 namespace {
 
@@ -25,22 +26,10 @@ __global__ __launch_bounds__(kUPThreads) void unproject_kernel(const DepthT* __r
   const int pix = blockIdx.x * kUPThreads + threadIdx.x;
   if (pix >= h * w) return;
   const int v = pix / w, u = pix - v * w;
-  const float* Ki = kinv + (size_t)bv * 9;
-  const float* Pm = pose + (size_t)bv * 16;
+  const UnprojectCam cm = unproject_cam(kinv + (size_t)bv * 9, pose + (size_t)bv * 16);
   const size_t p = (size_t)bv * h * w + pix;
-  float df;
-  if constexpr (sizeof(DepthT) == 2)
-    df = __fdiv_rn((float)depth[p], 1000.0f);  // np.asarray(png, float32) / 1000.  (:255)
-  else
-    df = depth[p];
-  const double d = (double)df, du = (double)u, dv = (double)v;
-  const double rx = ((double)Ki[0] * du + (double)Ki[1] * dv) + (double)Ki[2];
-  const double ry = ((double)Ki[3] * du + (double)Ki[4] * dv) + (double)Ki[5];
-  const double rz = ((double)Ki[6] * du + (double)Ki[7] * dv) + (double)Ki[8];
-  const double xc = rx * d, yc = ry * d, zc = rz * d;
-  const double xw = ((xc * (double)Pm[0] + yc * (double)Pm[1]) + zc * (double)Pm[2]) + (double)Pm[3];
-  const double yw = ((xc * (double)Pm[4] + yc * (double)Pm[5]) + zc * (double)Pm[6]) + (double)Pm[7];
-  const double zw = ((xc * (double)Pm[8] + yc * (double)Pm[9]) + zc * (double)Pm[10]) + (double)Pm[11];
+  double xw, yw, zw, zc;
+  unproject_pixel(cm, depth_metres(depth, p), u, v, xw, yw, zw, zc);  // unproject_core.h
   bool ok = zc > 0.0;  // :260
   if (box) {           // :274-281, x and y only, strict
     const float* bx = box + (size_t)(bv / nv) * 4;

@@ -82,3 +82,77 @@ def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_cl
             lo += o.size(0)
     logits = D.all_gather_logits(local, num_chunks)
     return D.vote_scene(logits, chunk_inds, n_pts)
+
+
+def chunk_base_masks(chunk_indices, base_point_ind, n_pts):
+    """bool (C, nb): base point j lies in chunk c (`base_point_mask[base_point_ind]` of scannet_2d3d.py:199-204, for all chunks).
+    Goes through a (C, n_pts) bool membership matrix: 12.8 MB for 64 chunks of a 200 000-point scene, C * n_pts bytes in general."""
+    dev = base_point_ind.device
+    C = len(chunk_indices)
+    member = torch.zeros((C, n_pts), dtype=torch.bool, device=dev)
+    if C:
+        rows = torch.repeat_interleave(torch.arange(C, device=dev), torch.tensor([int(c.numel()) for c in chunk_indices], device=dev))
+        member[rows, torch.cat(chunk_indices)] = True
+    return member[:, base_point_ind]
+
+
+def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
+                  min_nb_pts=2048, overlap=None, batch_size=8, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None,
+                  pad_generator=None):
+    """From a scene's raw arrays to what `infer_scene` takes: `ScanNet2D3DChunksTest.__getitem__` (mvpnet/data/scannet_2d3d.py:506-565)
+    followed by `get_rgbd_data`'s frame choice (:191-221) and the sparse-chunk rule of test_mvpnet_3d.py:146-154, on the device.
+
+    points (n,3) float32; depth (F,h,w) float32 m / (u)int16 mm with intrinsics cam_matrix ((3,3) or (4,4), of depth's resolution);
+    pose (F,4,4) float32; images (F,3,H,W) what the 2D network reads.  The overlap is computed from `depth` as given (the reference
+    uses 80x60 maps: chunks.compute_rgbd_overlap); the batches carry the lifting-resolution maps: `lift_depth` (F,H,W), or `depth`
+    itself when it already has the images' resolution, with the intrinsics' first two rows scaled by W/w and H/h (:206-210).
+    overlap=(base_point_ind, overlaps) -- the reference's per-scene arrays -- skips the overlap computation.
+
+    The result lists ALL chunks of the scene, i.e. what a single process hands to infer_scene; with several ranks every rank passes
+    infer_scene the batches of its own shard (dist.shard_chunks) and the full chunk_inds.  Beyond the reference's arguments:
+    `lift_depth`, `num_base_pts` / `radius` / `generator` (handed to chunks.compute_rgbd_overlap) and `pad_generator` (pad_sparse_chunk).
+    All chunks' frames are chosen by ONE ops.select_frames_batched call.  Every chunk is fed whole (nb_pts = -1), padded to
+    `min_nb_pts` by pad_sparse_chunk; consecutive chunks of equal size share a batch of up to `batch_size`, the chunk order is kept.
+    -> (chunk_batches, chunk_inds, n_pts) with the keys MVPNet3D._forward reads: images (B,nv,3,H,W), points (B,3,N), depth (B,nv,H,W),
+    cam_matrix / kinv (B,nv,3,3), pose (B,nv,4,4), pixel_box (B,4) = chunk box -/+ 0.1 m (:274-281), k."""
+    import numpy as np
+    from . import chunks as CH
+    from . import ops
+    dev = points.device
+    n_pts = points.size(0)
+    chunk_inds, boxes = CH.scene2chunks_legacy(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin, return_bbox=True)
+    if not chunk_inds:
+        return [], [], n_pts
+    if overlap is None:
+        overlap = CH.compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=num_base_pts, radius=radius, generator=generator)
+    base_point_ind, overlaps = overlap
+    base_point_ind = torch.as_tensor(base_point_ind).to(dev).long()
+    overlaps = torch.as_tensor(overlaps).to(dev)
+    picked = ops.select_frames_batched(overlaps if overlaps.dtype == torch.int32 else overlaps.bool(),
+                                       chunk_base_masks(chunk_inds, base_point_ind, n_pts), num_rgbd_frames)  # (C,nv)
+
+    ldepth = depth if lift_depth is None else lift_depth
+    F, H, W = ldepth.shape
+    if images.shape[0] != F or tuple(images.shape[-2:]) != (H, W):
+        raise RuntimeError('prepare_scene: images (F,3,H,W) and the lifting depth (F,H,W) disagree: pass lift_depth at the images\' resolution')
+    cam = (cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)).astype(np.float32)[..., :3, :3].copy()
+    cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
+    cam[..., 1, :] /= np.float32(depth.size(1) / H)
+    kinv = np.linalg.inv(cam)  # float32, :38
+    cam_t = torch.from_numpy(cam).to(dev).expand(F, 3, 3)
+    kinv_t = torch.from_numpy(np.ascontiguousarray(kinv)).to(dev).expand(F, 3, 3)
+    box = torch.stack(boxes)[:, [0, 1, 3, 4]]  # (C,4) float64 x1,y1,x2,y2
+    pixel_box = (box + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=box.device)).float().to(dev)
+
+    singles = [pad_sparse_chunk({'points': points[ind].t().contiguous()}, min_nb_pts=min_nb_pts, generator=pad_generator)['points'] for ind in chunk_inds]
+    chunk_batches, lo = [], 0
+    while lo < len(singles):
+        hi = lo + 1
+        while hi < len(singles) and hi - lo < batch_size and singles[hi].size(1) == singles[lo].size(1):
+            hi += 1
+        sel = picked[lo:hi]  # (B,nv)
+        chunk_batches.append({'images': images[sel].contiguous(), 'points': torch.stack(singles[lo:hi]).contiguous(), 'depth': ldepth[sel].contiguous(),
+                              'cam_matrix': cam_t[sel].contiguous(), 'kinv': kinv_t[sel].contiguous(), 'pose': pose[sel].contiguous(),
+                              'pixel_box': pixel_box[lo:hi].contiguous(), 'k': int(k)})
+        lo = hi
+    return chunk_batches, chunk_inds, n_pts

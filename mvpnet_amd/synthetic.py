@@ -119,3 +119,101 @@ def make_scene(scene_id, n_pts=200000, n_chunks=64, nb_pts=8192):
     (reference: mvpnet/utils/chunk_util.py:4-53, mvpnet/test_mvpnet_3d.py:142-164)."""
     rs = np.random.RandomState(77000 + scene_id)
     return [np.sort(rs.choice(n_pts, nb_pts, replace=False)).astype(np.int64) for _ in range(n_chunks)]
+
+
+def _ray_box(o, d, lo, hi):
+    """Entry distance of rays o + t d (o (3,), d (...,3)) into the axis-aligned box [lo, hi] (slab test); inf where they miss."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        t0 = (lo - o) / d
+        t1 = (hi - o) / d
+    tn = np.nanmax(np.minimum(t0, t1), axis=-1)
+    tf = np.nanmin(np.maximum(t0, t1), axis=-1)
+    return np.where((tn <= tf) & (tn > 0), tn, np.inf)
+
+
+def make_rgbd_scene(scene_id, n_frames, n_pts=60000, h=60, w=80, room=(6.5, 5.5, 2.5), n_boxes=4, jitter=0.005, dup_of=None):
+    """One synthetic RGB-D SCENE, what the reference's preprocessing reads per scan (preprocess.py:176-260): a room (floor z = 0,
+    four walls, `n_boxes` boxes along the walls), its jittered point cloud, and `n_frames` depth frames ray-cast in make_chunk's
+    style along a camera path.  The cameras stand on a ring of radius 1.6 m around the room's centre and look OUTWARD -- level,
+    up the walls and down at the floor in turn --, so walls, boxes and the outer floor are all seen while the floor inside the ring
+    is seen by no frame (a chunk there has all-zero overlap scores).  3 % of the depth pixels are invalid (0), frame n_frames // 2
+    has an `inf` pose (ScanNet marks lost tracking that way; preprocess.py:137-139 skips such frames) and the LAST frame repeats
+    frame `dup_of` (default n_frames // 3) exactly, which gives frame selection an exact score tie.
+    Returns host arrays: points (n_pts,3) f32, depth_mm (F,h,w) uint16, cam_matrix (4,4) f32 scaled to (h,w), kinv (3,3) f32,
+    pose (F,4,4) f32.  Seeded with RandomState(91000 + scene_id)."""
+    rs = np.random.RandomState(91000 + scene_id)
+    lx, ly, lz = room
+    centre = np.array([0.5 * lx, 0.5 * ly])
+    ring = 1.6
+    boxes = []
+    for i in range(n_boxes):  # along the walls, outside the ring
+        sx, sy, sz = rs.uniform(0.4, 0.9), rs.uniform(0.4, 0.9), rs.uniform(0.4, 1.2)
+        side = i % 4
+        along = rs.uniform(0.2, 0.8)
+        if side == 0:
+            x0, y0 = along * (lx - sx), 0.05
+        elif side == 1:
+            x0, y0 = lx - sx - 0.05, along * (ly - sy)
+        elif side == 2:
+            x0, y0 = along * (lx - sx), ly - sy - 0.05
+        else:
+            x0, y0 = 0.05, along * (ly - sy)
+        boxes.append((np.array([x0, y0, 0.0]), np.array([x0 + sx, y0 + sy, sz])))
+
+    # point cloud: area-weighted samples of the floor, the walls and the boxes' visible faces, jittered
+    surf = [(np.array([0, 0, 0.]), np.array([lx, 0, 0.]), np.array([0, ly, 0.])),
+            (np.array([0, 0, 0.]), np.array([lx, 0, 0.]), np.array([0, 0, lz])), (np.array([0, ly, 0.]), np.array([lx, 0, 0.]), np.array([0, 0, lz])),
+            (np.array([0, 0, 0.]), np.array([0, ly, 0.]), np.array([0, 0, lz])), (np.array([lx, 0, 0.]), np.array([0, ly, 0.]), np.array([0, 0, lz]))]
+    for lo, hi in boxes:
+        e = hi - lo
+        ex, ey, ez = np.array([e[0], 0, 0.]), np.array([0, e[1], 0.]), np.array([0, 0, e[2]])
+        surf += [(lo + ez, ex, ey), (lo, ex, ez), (lo + ey, ex, ez), (lo, ey, ez), (lo + ex, ey, ez)]
+    area = np.array([np.linalg.norm(np.cross(a, b)) for _, a, b in surf])
+    which = rs.choice(len(surf), n_pts, p=area / area.sum())
+    uv = rs.rand(n_pts, 2)
+    org = np.stack([s[0] for s in surf])[which]
+    ea = np.stack([s[1] for s in surf])[which]
+    eb = np.stack([s[2] for s in surf])[which]
+    points = (org + uv[:, :1] * ea + uv[:, 1:] * eb + rs.normal(0.0, jitter, (n_pts, 3))).astype(np.float32)
+
+    cam = np.eye(4, dtype=np.float32)
+    cam[0, 0] = cam[1, 1] = 577.87 * w / 640.0
+    cam[0, 2] = (w - 1) / 2.0
+    cam[1, 2] = (h - 1) / 2.0
+    kinv = np.linalg.inv(cam[:3, :3])  # float32, as scannet_2d3d.py:38
+
+    vv, uu = np.indices((h, w))
+    rays_cam = np.stack([(uu - cam[0, 2]) / cam[0, 0], (vv - cam[1, 2]) / cam[1, 1], np.ones_like(uu, float)], -1)
+    pitches = np.deg2rad([0.0, -35.0, 20.0, -55.0])  # level, floor-facing, up the wall, steeply down
+    poses, depths = [], []
+    for i in range(n_frames):
+        az = 2.0 * np.pi * (i + rs.uniform(-0.3, 0.3)) / max(n_frames - 1, 1) * 3.0  # three turns around the ring
+        pitch = pitches[i % 4] + np.deg2rad(rs.uniform(-5.0, 5.0))
+        out = np.array([np.cos(az), np.sin(az), 0.0])
+        pos = np.array([centre[0], centre[1], 0.0]) + ring * out + np.array([0.0, 0.0, rs.uniform(1.1, 1.6)])
+        pose = _look_at(pos, pos + np.cos(pitch) * out + np.array([0.0, 0.0, np.sin(pitch)]))
+        rays_w = rays_cam @ pose[:3, :3].astype(np.float64).T
+        o = pose[:3, 3].astype(np.float64)
+        t = [_ray_box(o, rays_w, lo, hi) for lo, hi in boxes]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            t.append(np.where(rays_w[..., 2] < 0, -o[2] / rays_w[..., 2], np.inf))              # floor
+            t.append(np.where(rays_w[..., 0] < 0, -o[0] / rays_w[..., 0], np.inf))              # wall x = 0
+            t.append(np.where(rays_w[..., 0] > 0, (lx - o[0]) / rays_w[..., 0], np.inf))        # wall x = lx
+            t.append(np.where(rays_w[..., 1] < 0, -o[1] / rays_w[..., 1], np.inf))              # wall y = 0
+            t.append(np.where(rays_w[..., 1] > 0, (ly - o[1]) / rays_w[..., 1], np.inf))        # wall y = ly
+        z = np.min(np.stack(t, -1), axis=-1)  # depth along camera z because rays_cam[...,2] == 1
+        hit_z = o[2] + z * rays_w[..., 2]
+        z = np.where(np.isfinite(z) & (z < 6.5) & (hit_z <= lz), z, 0.0)  # above the walls: open ceiling, no return
+        mm = np.round(z * 1000.0).astype(np.uint16)
+        mm[rs.rand(h, w) < 0.03] = 0  # invalid depth
+        poses.append(pose)
+        depths.append(mm)
+    depth_mm = np.stack(depths)
+    pose = np.stack(poses)
+    if n_frames >= 2:
+        src = n_frames // 3 if dup_of is None else int(dup_of)
+        depth_mm[-1] = depth_mm[src]
+        pose[-1] = pose[src]
+    if n_frames >= 3:
+        pose[n_frames // 2] = np.inf
+    return dict(points=points, depth_mm=depth_mm, cam_matrix=cam, kinv=kinv.astype(np.float32), pose=pose)
