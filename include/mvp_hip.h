@@ -837,6 +837,29 @@ int mvp_vote_gather_f32(const float* logit, int64_t ld_chunk, int64_t ld_r, int6
                         mvp_stream_t stream);
 int mvp_vote_finish_f32(const float* sum, const int32_t* count, int64_t n_pts, int64_t C, float* mean, int64_t* label,
                         mvp_stream_t stream);
+/* whole-scene voting (mvpnet/test_3d_scene.py:152-164: per vote a scikit-learn ball tree over the vote's sampled points on the host,
+ * `pred_logit_whole_scene += seg_logit_per_vote[nn_indices[:, 0]]`): all votes in ONE query launch behind one grid-build launch.
+ * points (n,3): the scene's points, shared by all votes.  key (V,nb,3): the sampled points of each vote.  logit: element (v,j,c) at
+ * logit[v*ld_vote + j*ld_r + c*ld_c], so the network's (V,C,nb) output goes in with its own strides, row-major storage included.
+ *   nearest key: nn_v(p) = the key j of vote v with the smallest float32 (dx*dx + dy*dy) + dz*dz to p (each operation rounded once,
+ *     never contracted: the expression of every index kernel here); among equal distances the LOWEST key index wins.
+ *   sum (n,C), WRITTEN: sum[p,c] = (...(logit[0,nn_0(p),c] + logit[1,nn_1(p),c]) + ...) in vote order in float32, without atomics:
+ *     bit-reproducible, and the reference's `+=` on a zeroed array.  Division by the number of votes and the argmax (first maximum) are
+ *     mvp_vote_finish_f32 with a count of V for every point.
+ *   nn_index (V,n) int64 or NULL: nn_v(p).
+ *   swept: NULL, or one int32 counter ZEROED by the caller: += 1 for every (point, vote) whose search swept all nb keys because the
+ *     27 cells around the point did not certify their minimum (and for every one when nb < 256, where there is no grid).
+ *   non-finite coordinates: no fault, no hang; a point or key with a NaN / inf coordinate is never a nearest pair (such distances do
+ *     not compare), a row without any comparable key gets index 0; rows whose point is finite are exact over the finite keys, and
+ *     every index lies in [0, nb).
+ * EINVAL before any launch unless 0 <= n < 2^31, 1 <= nb <= 65536, 1 <= V < 65536, 1 <= C <= 64, and -- when
+ * mvp_vote_nearest_workspace(V, nb) > 0 -- workspace_bytes >= that figure and workspace 16-byte aligned.
+ * mvp_vote_nearest_workspace: V * (16 nb + 16512) bytes of device scratch, reusable once the launches have run (stream order);
+ * 0 for nb < 256 (the keys are swept, workspace may be NULL) and for shapes the call refuses. */
+int64_t mvp_vote_nearest_workspace(int64_t V, int64_t nb);
+int mvp_vote_nearest_f32(const float* points, int64_t n, const float* key, int64_t V, int64_t nb, const float* logit, int64_t ld_vote,
+                         int64_t ld_r, int64_t ld_c, int64_t C, float* sum, int64_t* nn_index, int32_t* swept, void* workspace,
+                         int64_t workspace_bytes, mvp_stream_t stream);
 
 /* ---- segmentation loss and confusion matrix (the step after the path) -------------
  * Logits are addressed as element (b,c,n) at logit[b*ld_b + c*ld_c + n*ld_n]: the reference's (B,C,N) tensor

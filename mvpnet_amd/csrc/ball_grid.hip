@@ -24,6 +24,19 @@
 // when the third distance is below 0.999 x the distance from the query to the nearest face of the 27-cell block that has keys beyond it
 // (every key outside the block is then strictly farther).  Otherwise the 16 lanes sweep all keys for that query: exact on every input,
 // fast where the keys are spread like a sampled surface or volume.
+//
+// Whole-scene voting (mvpnet/test_3d_scene.py:152-164: a scikit-learn ball tree per vote on the host, `pred_logit_whole_scene +=
+// seg_logit_per_vote[nn_indices[:, 0]]`) is the 1-NN case of the same search with the accumulation fused: one grid per vote, 16 lanes per
+// scene point keep ONE packed (distance, index) minimum each over the 27 cells' keys, the DPP row minimum merges them -- the packed compare
+// is `smaller distance, then lower key index` --, and the winner's logit row is added to registers, vote after vote, so every `sum` row is
+// written once and the additions run in vote order without atomics.  Exactness: every key is tested with the same dist2_3(key, query);
+// the minimum over the block stands when it is below (0.999 margin)^2, margin = the query's distance to the nearest face of the 27-cell
+// block that has cells beyond it: a key outside the block lies at least two cells from the query's cell on some axis, i.e. beyond that
+// axis' face (cell coordinates carry <= 3e-6 cells of error, the 0.1 % pays for it and for the rounding of d), hence at a distance
+// >= margin > sqrt(d): strictly farther, so it can neither win nor tie.  Anything else -- an empty block, a query far outside the keys'
+// box, a query without any comparable distance (non-finite coordinates: the minimum stays +inf) -- sweeps all keys of that vote with the same
+// 16 lanes and the same packed minimum.  A block that reaches the grid's border on every side (margin = +inf: at most three cells per axis, a
+// zero-extent cloud's single cell among them) holds every key, so its finite minimum stands without a sweep.
 #include <cfloat>
 #include <cstdlib>
 
@@ -341,6 +354,45 @@ __device__ __forceinline__ void row_merge3(unsigned long long (&b)[3]) {
   b[2] = r[2];
 }
 
+// The 27 cells around cell c as nine record runs (x is the fastest cell axis): lo[r] = first record of run r, cum[r] = records in the runs
+// before it, cum[9] = all of them.  Shared by the 3-NN and the nearest-key search.
+__device__ __forceinline__ void block_runs(const int (&c)[3], const int (&g)[3], const int* __restrict__ st, int (&lo)[9], int (&cum)[10]) {
+  cum[0] = 0;
+  const int xlo = max(c[0] - 1, 0), xhi = min(c[0] + 1, g[0] - 1);
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int zz = c[2] + r / 3 - 1, yy = c[1] + r % 3 - 1;
+    const bool in = zz >= 0 && zz < g[2] && yy >= 0 && yy < g[1];
+    const int base = (zz * g[1] + yy) * g[0];
+    const int a0 = in ? st[base + xlo] : 0, e0 = in ? st[base + xhi + 1] : 0;
+    lo[r] = a0;
+    cum[r + 1] = cum[r] + (e0 - a0);
+  }
+}
+// record index of flat position f of the runs' concatenation
+__device__ __forceinline__ int block_record(int f, const int (&lo)[9], const int (&cum)[10]) {
+  int j = lo[0] + f;
+#pragma unroll
+  for (int r = 1; r < 9; ++r)
+    if (f >= cum[r]) j = lo[r] + (f - cum[r]);
+  return j;
+}
+// Distance from q to the nearest face of the 27-cell block that has cells beyond it; +inf when the block reaches the grid's border on every
+// side (then it holds every key).  The ONE certification rule of both searches: a distance below (0.999 margin)^2 cannot be beaten or
+// tied by a key outside the block.
+__device__ __forceinline__ float block_margin(const float (&q)[3], const int (&c)[3], const float (&mn)[3], const float (&inv)[3], const int (&g)[3]) {
+  float margin = INFINITY;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (inv[a] > 0.f) {
+      const float cell = 1.f / inv[a];
+      if (c[a] >= 2) margin = fminf(margin, q[a] - (mn[a] + (float)(c[a] - 1) * cell));
+      if (c[a] + 2 < g[a]) margin = fminf(margin, (mn[a] + (float)(c[a] + 2) * cell) - q[a]);
+    }
+  }
+  return margin;
+}
+
 __global__ __launch_bounds__(kQueryThreads) void knn3_grid_kernel(const float* __restrict__ query, const float* __restrict__ key, int N1, int N2,
                                                                   const int* __restrict__ heads, const int* __restrict__ starts,
                                                                   const float4* __restrict__ sorted, int64_t* __restrict__ index,
@@ -362,19 +414,7 @@ __global__ __launch_bounds__(kQueryThreads) void knn3_grid_kernel(const float* _
 #pragma unroll
   for (int a = 0; a < 3; ++a) c[a] = cell_of(q[a], mn[a], inv[a], g[a]);
   int lo[9], cum[10];
-  cum[0] = 0;
-  {
-    const int xlo = max(c[0] - 1, 0), xhi = min(c[0] + 1, g[0] - 1);
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-      const int zz = c[2] + r / 3 - 1, yy = c[1] + r % 3 - 1;
-      const bool in = zz >= 0 && zz < g[2] && yy >= 0 && yy < g[1];
-      const int base = (zz * g[1] + yy) * g[0];
-      const int a0 = in ? st[base + xlo] : 0, e0 = in ? st[base + xhi + 1] : 0;
-      lo[r] = a0;
-      cum[r + 1] = cum[r] + (e0 - a0);
-    }
-  }
+  block_runs(c, g, st, lo, cum);
   unsigned long long best[3] = {kKnnEmpty, kKnnEmpty, kKnnEmpty};
   const int T = cum[9];
   for (int f0 = l16; f0 < T; f0 += kInFlight * kLanesPerQuery) {
@@ -382,26 +422,14 @@ __global__ __launch_bounds__(kQueryThreads) void knn3_grid_kernel(const float* _
 #pragma unroll
     for (int u = 0; u < kInFlight; ++u) {
       const int f = f0 + u * kLanesPerQuery;
-      int j = lo[0] + f;
-#pragma unroll
-      for (int r = 1; r < 9; ++r)
-        if (f >= cum[r]) j = lo[r] + (f - cum[r]);
-      p[u] = f < T ? sp[j] : make_float4(NAN, NAN, NAN, 0.f);  // a NaN distance never enters
+      p[u] = f < T ? sp[block_record(f, lo, cum)] : make_float4(NAN, NAN, NAN, 0.f);  // a NaN distance never enters
     }
 #pragma unroll
     for (int u = 0; u < kInFlight; ++u) top3_insert(best, dist2_3(p[u].x, p[u].y, p[u].z, q[0], q[1], q[2]), __float_as_int(p[u].w));
   }
   row_merge3(best);
   // does anything outside the 27 cells come closer than the third?  Faces of the block with cells beyond them, 0.1 % inside.
-  float margin = INFINITY;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (inv[a] > 0.f) {
-      const float cell = 1.f / inv[a];
-      if (c[a] >= 2) margin = fminf(margin, q[a] - (mn[a] + (float)(c[a] - 1) * cell));
-      if (c[a] + 2 < g[a]) margin = fminf(margin, (mn[a] + (float)(c[a] + 2) * cell) - q[a]);
-    }
-  }
+  const float margin = block_margin(q, c, mn, inv, g);
   const float m = margin * 0.999f;
   const float d3 = __uint_as_float((unsigned)(best[2] >> 32));
   if (!(margin == INFINITY || (m > 0.f && d3 < m * m))) {  // (a NaN margin -- a non-finite query -- lands here too: its distances are NaN either way)
@@ -452,6 +480,106 @@ inline int knn_grid_axis(int64_t N2) {
 
 inline int64_t grid_rows(int64_t N2) { return cdiv(N2, 128 * kLanesPerQuery); }
 inline int64_t grid_bytes(int64_t B, int64_t N2) { return B * ((int64_t)sizeof(int) * (kGridHead + kGridStarts) + (int64_t)sizeof(float4) * N2); }
+
+// ---- nearest key of V clouds + logit accumulation (whole-scene voting) ---------------------------------------------------------------
+constexpr int kVoteMaxCols = 64;                                   // logit columns: kVoteMaxCols / kLanesPerQuery registers per lane
+constexpr int kVoteColsPerLane = kVoteMaxCols / kLanesPerQuery;
+constexpr int64_t kVoteGridMinKeys = 256, kVoteMaxKeys = 65536;
+
+__device__ __forceinline__ void top1_insert(unsigned long long& b, float d, int id) {
+  if (d < INFINITY) {  // NaN and +inf never enter
+    const unsigned long long k = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id;  // d >= +0: the bits order like the value
+    b = k < b ? k : b;
+  }
+}
+
+__global__ __launch_bounds__(kQueryThreads) void vote_nearest_kernel(const float* __restrict__ points, int n, const float* __restrict__ key, int V,
+                                                                     int nb, const float* __restrict__ logit, int64_t ld_vote, int64_t ld_r,
+                                                                     int64_t ld_c, int C, const int* __restrict__ heads,
+                                                                     const int* __restrict__ starts, const float4* __restrict__ sorted,
+                                                                     float* __restrict__ sum, int64_t* __restrict__ nn_index,
+                                                                     int* __restrict__ swept) {
+  const int tid = threadIdx.x;
+  const int grp = tid / kLanesPerQuery, l16 = tid & (kLanesPerQuery - 1);
+  const int64_t qi = (int64_t)blockIdx.x * kQueriesPerWg + grp;
+  if (qi >= n) return;  // whole 16-lane rows leave together
+  const float q[3] = {points[qi * 3], points[qi * 3 + 1], points[qi * 3 + 2]};
+  float acc[kVoteColsPerLane];
+#pragma unroll
+  for (int k = 0; k < kVoteColsPerLane; ++k) acc[k] = 0.f;
+
+  for (int v = 0; v < V; ++v) {
+    const float* kp = key + (size_t)v * nb * 3;
+    unsigned long long best = kKnnEmpty;
+    bool certified = false;
+    if (heads != nullptr) {  // (uniform: clouds of fewer than kVoteGridMinKeys keys have no grid)
+      const int* hd = heads + (size_t)v * kGridHead;
+      const float mn[3] = {__int_as_float(hd[0]), __int_as_float(hd[1]), __int_as_float(hd[2])};
+      const float inv[3] = {__int_as_float(hd[3]), __int_as_float(hd[4]), __int_as_float(hd[5])};
+      const int g[3] = {hd[6], hd[7], hd[8]};
+      const int* st = starts + (size_t)v * kGridStarts;
+      const float4* sp = sorted + (size_t)v * nb;
+      int c[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) c[a] = cell_of(q[a], mn[a], inv[a], g[a]);
+      int lo[9], cum[10];
+      block_runs(c, g, st, lo, cum);
+      const int T = cum[9];
+      for (int f0 = l16; f0 < T; f0 += kInFlight * kLanesPerQuery) {
+        float4 p[kInFlight];
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) {
+          const int f = f0 + u * kLanesPerQuery;
+          p[u] = f < T ? sp[block_record(f, lo, cum)] : make_float4(NAN, NAN, NAN, 0.f);  // a NaN distance never enters
+        }
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) top1_insert(best, dist2_3(p[u].x, p[u].y, p[u].z, q[0], q[1], q[2]), __float_as_int(p[u].w));
+      }
+      best = row_min64(best);
+      // does anything outside the 27 cells come as close?  Faces of the block with cells beyond them, 0.1 % inside.
+      const float m = block_margin(q, c, mn, inv, g) * 0.999f;
+      const float d1 = __uint_as_float((unsigned)(best >> 32));
+      // An empty block has d1 = +inf and is refused.  So is a non-finite query: all its distances are NaN / +inf, none enters, d1 stays
+      // +inf (its margin proves nothing: fminf drops NaN operands).  A margin of +inf -- no face with cells beyond it, e.g. a zero-extent
+      // cloud with one cell per axis -- means the block holds every key: any finite minimum stands, exactly.
+      certified = m > 0.f && d1 < m * m;
+    }
+    if (!certified) {
+      best = kKnnEmpty;
+      for (int j0 = l16; j0 < nb; j0 += kInFlight * kLanesPerQuery) {
+        float x[kInFlight], y[kInFlight], z[kInFlight];
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) {
+          const int j = j0 + u * kLanesPerQuery;
+          const bool in = j < nb;
+          x[u] = in ? kp[(size_t)j * 3] : NAN;
+          y[u] = in ? kp[(size_t)j * 3 + 1] : NAN;
+          z[u] = in ? kp[(size_t)j * 3 + 2] : NAN;
+        }
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) top1_insert(best, dist2_3(x[u], y[u], z[u], q[0], q[1], q[2]), j0 + u * kLanesPerQuery);
+      }
+      best = row_min64(best);
+      if (swept != nullptr && l16 == 0) atomicAdd(swept, 1);
+    }
+    const int j = best == kKnnEmpty ? 0 : (int)(unsigned)best;  // no finite distance at all (non-finite input): key 0
+    if (nn_index != nullptr && l16 == 0) nn_index[(size_t)v * n + qi] = j;
+    const float* lp = logit + v * ld_vote + j * ld_r;
+#pragma unroll
+    for (int k = 0; k < kVoteColsPerLane; ++k) {
+      const int col = l16 + k * kLanesPerQuery;
+      if (col < C) {
+        const float x = lp[col * ld_c];
+        acc[k] = v == 0 ? x : acc[k] + x;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kVoteColsPerLane; ++k) {
+    const int col = l16 + k * kLanesPerQuery;
+    if (col < C) sum[qi * C + col] = acc[k];
+  }
+}
 
 }  // namespace
 
@@ -530,5 +658,43 @@ MVP_API int mvp_knn3_grid_f32(const float* query, const float* key, int64_t B, i
   dim3 grid((unsigned)cdiv(N1, kQueriesPerWg), (unsigned)B);
   hipLaunchKernelGGL(knn3_grid_kernel, grid, dim3(kQueryThreads), 0, s, query, key, (int)N1, (int)N2, heads, starts, sorted, index, distance,
                      weight, eps);
+  return mvp_launch_status();
+}
+
+// Whole-scene voting (include/mvp_hip.h): for every scene point and every vote the nearest of that vote's nb keys, the winners' logit rows
+// added in vote order.  mvp_vote_nearest_workspace: V * (16 nb + 16512) bytes of scratch for the V grids, 0 below 256 keys (no grid: the
+// 16 lanes sweep the keys) and for shapes the call refuses.
+MVP_API int64_t mvp_vote_nearest_workspace(int64_t V, int64_t nb) {
+  if (V <= 0 || V >= 65536 || nb < kVoteGridMinKeys || nb > kVoteMaxKeys) return 0;
+  return grid_bytes(V, nb);
+}
+
+MVP_API int mvp_vote_nearest_f32(const float* points, int64_t n, const float* key, int64_t V, int64_t nb, const float* logit, int64_t ld_vote,
+                                 int64_t ld_r, int64_t ld_c, int64_t C, float* sum, int64_t* nn_index, int32_t* swept, void* workspace,
+                                 int64_t workspace_bytes, mvp_stream_t stream) {
+  MVP_NONNULL(points);
+  MVP_NONNULL(key);
+  MVP_NONNULL(logit);
+  MVP_NONNULL(sum);
+  MVP_REQUIRE(n >= 0 && n < (1ll << 31));
+  MVP_REQUIRE(nb >= 1 && nb <= kVoteMaxKeys && V >= 1 && V < 65536 && C >= 1 && C <= kVoteMaxCols);
+  const int64_t need = mvp_vote_nearest_workspace(V, nb);
+  if (need > 0) {
+    MVP_NONNULL(workspace);
+    MVP_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
+  }
+  if (n == 0) return MVP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float4* sorted = nullptr;
+  int *starts = nullptr, *heads = nullptr;
+  if (need > 0) {  // layout as in the siblings: records first (16-byte aligned), then the starts, then the heads
+    sorted = static_cast<float4*>(workspace);
+    starts = reinterpret_cast<int*>(sorted + (size_t)V * nb);
+    heads = starts + (size_t)V * kGridStarts;
+    hipLaunchKernelGGL(ball_grid_build_kernel, dim3((unsigned)V), dim3(kBuildThreads), 0, s, key, (int)nb, 0.f, knn_grid_axis(nb), heads, starts,
+                       sorted);
+  }
+  hipLaunchKernelGGL(vote_nearest_kernel, dim3((unsigned)cdiv(n, kQueriesPerWg)), dim3(kQueryThreads), 0, s, points, (int)n, key, (int)V, (int)nb,
+                     logit, ld_vote, ld_r, ld_c, (int)C, heads, starts, sorted, sum, nn_index, swept);
   return mvp_launch_status();
 }

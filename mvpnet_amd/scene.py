@@ -84,6 +84,65 @@ def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_cl
     return D.vote_scene(logits, chunk_inds, n_pts)
 
 
+def infer_scene_votes(model, points, feature=None, nb_pts=32768, num_votes=3, vote_inds=None, generator=None):
+    """The whole-scene test path of the 3D baseline (mvpnet/test_3d_scene.py:127-164, configs/scannet/3d_baselines/pn2ssg_scene.yaml):
+    `num_votes` random subsamples of the scene go through `model` as ONE batch, every subsample's logits are propagated to all scene
+    points through each point's nearest sampled point, and the votes are averaged.  Single process.
+    model: PN2SSG (anything that maps {'points' (V,3,nb), ['feature' (V,3,nb)]} to {'seg_logit' (V,C,nb)}) on the points' GPU.
+    points (n,3) float32 on the device; feature (n,3) float32 or None: the colours, for a model with in_channels = 3.
+    vote_inds (V,nb_pts) int64 in [0, n): the subsamples, instead of the draw -- nb_pts, num_votes and generator are then NOT used, the
+    tensor's shape decides -- (the reference's np.random.choice draws can be replayed exactly);
+    otherwise per vote, as :128-131, `torch.randperm(n, generator=generator)[:nb_pts]` when n >= nb_pts -- the generator's device
+    decides where the permutation is drawn --, else arange(n) followed by nb_pts - n times index 0 (the reference's np.zeros padding).
+    -> mean logits (n,C), labels (n,) -- every point gets one, this path has no "no prediction" class --, vote_inds (V,nb_pts).
+    The propagation is ops.vote_nearest (nearest by float32 distance, lowest index on ties, votes added in order), the division by the
+    number of votes and the argmax are mvp_vote_finish_f32."""
+    from . import _lib as L
+    from . import ops
+    dev = points.device
+    n = points.size(0)
+    if points.dim() != 2 or points.size(1) != 3 or n < 1:
+        raise RuntimeError('infer_scene_votes: points must be (n,3), n >= 1')
+    if feature is not None and (feature.dim() != 2 or feature.size(0) != n):
+        raise RuntimeError('infer_scene_votes: feature must be (n,channels)')
+    if vote_inds is None:
+        if not (1 <= num_votes < 65536 and 1 <= nb_pts <= ops.vote.MAX_KEYS):
+            raise RuntimeError('infer_scene_votes: needs 1 <= num_votes < 65536 and 1 <= nb_pts <= {}'.format(ops.vote.MAX_KEYS))
+        picks = []
+        for _ in range(int(num_votes)):
+            if n >= nb_pts:
+                gdev = generator.device if generator is not None else dev
+                picks.append(torch.randperm(n, generator=generator, device=gdev)[:nb_pts].to(dev))
+            else:
+                picks.append(torch.cat([torch.arange(n, device=dev), torch.zeros(nb_pts - n, dtype=torch.int64, device=dev)]))
+        vote_inds = torch.stack(picks)
+    else:
+        # checked before the forward pass, not after it (the range check reads two numbers back from the device)
+        vote_inds = torch.as_tensor(vote_inds).to(dev).long()
+        if vote_inds.dim() != 2 or not (1 <= vote_inds.size(0) < 65536 and 1 <= vote_inds.size(1) <= ops.vote.MAX_KEYS):
+            raise RuntimeError('infer_scene_votes: vote_inds must be (V,nb_pts) with 1 <= V < 65536 and 1 <= nb_pts <= {}'.format(ops.vote.MAX_KEYS))
+        if int(vote_inds.min()) < 0 or int(vote_inds.max()) >= n:
+            raise RuntimeError('infer_scene_votes: vote_inds must lie in [0, {})'.format(n))
+    V = vote_inds.size(0)
+    keys = points[vote_inds]  # (V,nb,3)
+    batch = {'points': keys.transpose(1, 2).contiguous()}
+    if feature is not None:
+        batch['feature'] = feature[vote_inds].transpose(1, 2).contiguous()
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            logit = model(batch)['seg_logit']  # (V,C,nb), PN2SSG: a transposed view of row-major rows
+    finally:
+        model.train(was_training)
+    total = ops.vote_nearest(points.contiguous(), keys, logit)
+    count = torch.full((n,), V, dtype=torch.int32, device=dev)
+    mean = torch.empty_like(total)
+    label = torch.empty(n, dtype=torch.int64, device=dev)
+    L.call('mvp_vote_finish_f32', total, L.ptr(total), L.ptr(count), n, total.size(1), L.ptr(mean), L.ptr(label))
+    return mean, label, vote_inds
+
+
 def chunk_base_masks(chunk_indices, base_point_ind, n_pts):
     """bool (C, nb): base point j lies in chunk c (`base_point_mask[base_point_ind]` of scannet_2d3d.py:199-204, for all chunks).
     Goes through a (C, n_pts) bool membership matrix: 12.8 MB for 64 chunks of a 200 000-point scene, C * n_pts bytes in general."""
