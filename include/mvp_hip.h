@@ -309,6 +309,60 @@ int mvp_frame_overlap_u16(const uint16_t* depth_mm, const float* kinv, const flo
 int mvp_select_frames_u32(const uint32_t* overlap_bits, const uint32_t* chunk_bits, int64_t F, int64_t C, int64_t W, int64_t n_pick,
                           int64_t* picked, int32_t* gain, mvp_stream_t stream);
 
+/* the same greedy selection for chunks of DIFFERENT scenes (a training batch): overlap_bits (Ftot,W) holds all scenes' frame rows
+ * one scene after the other; chunk c chooses among rows [frame_begin[c], frame_begin[c] + frame_count[c]) only (both (C,) int64 ON THE
+ * DEVICE), by the rule above with the lowest row on ties, and gets GLOBAL row indices in picked (C,n_pick); gain as above.
+ * frame_count[c] >= 1 and the range inside [0, Ftot) are the caller's, like any index array's contents (the entry cannot read the
+ * device arrays without a synchronisation): a range is cut to [0, Ftot) and a chunk left with no frame gets picked = -1, gain = 0 --
+ * no row outside the matrix is read.  Ftot >= 1 (MVP_EINVAL: no chunk could have a frame); W <= 1024, MVP_EUNSUPPORTED beyond. */
+int mvp_select_frames_ranges_u32(const uint32_t* overlap_bits, const uint32_t* chunk_bits, const int64_t* frame_begin,
+                                 const int64_t* frame_count, int64_t Ftot, int64_t C, int64_t W, int64_t n_pick, int64_t* picked,
+                                 int32_t* gain, mvp_stream_t stream);
+
+/* ---- training chunks (NEW on the device; the reference draws them in a data-loader worker) ----
+ * One call draws B training chunks from resident scenes: ScanNet2D3DChunks.__getitem__ (mvpnet/data/scannet_2d3d.py:341-381) and the
+ * base-point mask of get_rgbd_data (:199-204), without a host synchronisation and without an allocation (graph-capturable).
+ *   points (Ntot,3) float32, seg_label (Ntot,) int64: S scenes one after the other, labels already mapped (negative = unlabelled);
+ *   scene_offsets (S+1,) int64; scene_of_chunk (B,) int64 (a scene may occur more than once); center_ind (B,T) int64: the centres to
+ *   try, point indices inside the chunk's scene (the reference tries T = 10); base_point_ind (S,nbp) int64 indices inside each scene, or
+ *   NULL with nbp = 0.  All on the device.  Index arrays' contents are the caller's: out-of-range values are clamped into the arrays
+ *   (a wrong result, never a stray access).
+ * The try rule, in float32, each operation rounded once, never contracted (float32 chunk_size / chunk_margin as in :134-136):
+ *   c = xy[center_ind[b,t]];  lo = (c - 0.5f*size) - margin;  hi = (c + 0.5f*size) + margin   (size, margin rounded to float32 first)
+ *   point j is a member iff x >= lo.x && x <= hi.x && y >= lo.y && y <= hi.y (inclusive; a NaN coordinate is never a member);
+ *   m = members, l = members with label >= 0; try t passes iff m > 0 && (double)l / (double)m >= chunk_thresh (numpy.mean of a bool
+ *   array against the Python float, :358-362).  The first passing t wins: try_index[b] = t, chunk_box[b] = (lo.x, lo.y, hi.x, hi.y).
+ * Fallback (:364-369), no try passes: try_index = -1, EVERY point of the scene is a member, chunk_box = (min_xy - margin, max_xy + margin)
+ *   in float32 (numpy.min / max: a NaN coordinate makes that bound NaN).
+ * bounds_f64 != 0: lo, hi in float64 from the float32 centre and the float64 size / margin, float32 coordinates compared as doubles --
+ *   ScanNet3DChunks (mvpnet/data/scannet_3d.py:128-162); chunk_box holds the bounds rounded to float32.
+ * Resampling to nb_pts (:374-381; the reference's law, the draws are a counter hash as for the dropout mask): h = lowbias32
+ *   (csrc/dropout.h), seed32 = low ^ high word of the seed (*seed_device when that pointer is not NULL: one int64 ON THE DEVICE, so a
+ *   replayed graph can draw afresh; else `seed`), s_b = h(seed32 + 0x9E3779B9 * (b+1)), members = the member indices, ascending.
+ *   pad (m < nb_pts):  choice[b,s] = members[s] for s < m, members[((uint64)h(s ^ s_b ^ 0x85EBCA6B) * m) >> 32] for s >= m;
+ *   crop (m >= nb_pts): the member with point index j has key h(j ^ s_b) -- h is a bijection, the keys of a chunk are distinct --,
+ *     choice[b,s] = the member with the s-th smallest key: a random subset in random ORDER (not in mesh-vertex order, which would bias
+ *     ball query's first-32 rule and FPS's start at slot 0).
+ * Outputs: choice (B,nb_pts) int64 indices inside the scene; out_points (B,3,nb_pts) float32; out_label (B,nb_pts) int64; chunk_box
+ *   (B,4) float32; try_index (B,), num_members (B,) int32; base_bits (B,ceil(nbp/32)) uint32 when nbp > 0: bit j % 32 of word j / 32 =
+ *   base point j of the chunk's scene is a member (the rows mvp_select_frames_ranges_u32 reads; padding bits zero).
+ * Every result is a function of the arguments alone (integer counts, distinct keys): bit-reproducible.
+ * Limits: nb_pts <= MVP_SAMPLE_MAX_PTS (the crop sorts its (key, index) pairs in 64 KiB of LDS), T <= MVP_SAMPLE_MAX_TRIES,
+ *   Ntot < 2^31 (so every scene's n < 2^31), B <= MVP_SAMPLE_MAX_CHUNKS: MVP_EUNSUPPORTED beyond, nothing is launched.  MVP_EINVAL
+ *   unless Ntot, S, T, nb_pts >= 1, B, nbp >= 0, no NaN among size / margin / chunk_thresh, workspace 16-byte aligned with
+ *   workspace_bytes >= mvp_sample_chunks_workspace(Ntot, B, T, nb_pts) (0 for shapes the call refuses).  The scratch is reusable once
+ *   the launches have run (stream order). */
+#define MVP_SAMPLE_MAX_PTS 8192
+#define MVP_SAMPLE_MAX_TRIES 32
+#define MVP_SAMPLE_MAX_CHUNKS 65535
+int64_t mvp_sample_chunks_workspace(int64_t Ntot, int64_t B, int64_t T, int64_t nb_pts);
+int mvp_sample_chunks_f32(const float* points, const int64_t* seg_label, const int64_t* scene_offsets, const int64_t* scene_of_chunk,
+                          const int64_t* center_ind, const int64_t* base_point_ind, int64_t Ntot, int64_t S, int64_t B, int64_t T,
+                          int64_t nbp, int64_t nb_pts, double size_x, double size_y, double margin_x, double margin_y,
+                          double chunk_thresh, int bounds_f64, uint64_t seed, const int64_t* seed_device, int64_t* choice,
+                          float* out_points, int64_t* out_label, float* chunk_box, int32_t* try_index, int32_t* num_members,
+                          uint32_t* base_bits, void* workspace, int64_t workspace_bytes, mvp_stream_t stream);
+
 /* Column slices of several row-major float matrices in one launch (host-side helper of the shared-MLP path: the reference slices
  * nothing -- it concatenates the inputs instead, modules.py:32-35,178-186 -- the linear-first factorisation of those layers needs
  * each column group of the weight as its own aligned operand).  table: n x 6 int64 ON THE DEVICE, per entry

@@ -69,6 +69,28 @@ def crop_pad_choice(n, nb_pts, generator=None, device=None):
     return torch.randperm(n, generator=generator, device=device)[:nb_pts]
 
 
+def sample_train_chunks(points, seg_label, scene_offsets, scene_of_chunk, nb_pts, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2),
+                        chunk_thresh=0.3, num_tries=10, base_point_ind=None, bounds_f64=False, generator=None):
+    """A training batch of chunks drawn on the device: `ScanNet2D3DChunks.__getitem__`'s random chunk and resampling
+    (scannet_2d3d.py:341-381) for B dataset indices at once, without a host synchronisation.  points (Ntot,3) float32 / seg_label (Ntot,)
+    int64: the resident scenes one after the other, scene_offsets (S+1,) int64, scene_of_chunk (B,) int64, all on the device.
+    The `num_tries` centres of every chunk (`np.random.randint(n)` per try in the reference) and the resampling seed are drawn ON THE
+    DEVICE from `generator` (a generator of that device, or its global one): the same law as the reference, not the same draws.
+    -> ops.sample_chunks' dict (choice, points (B,3,nb_pts), seg_label, chunk_box, try_index, num_members [, base_bits]) + the draws:
+    center_ind (B,num_tries) int64 and seed (1,) int64, on the device."""
+    from . import ops
+    dev = points.device
+    n = (scene_offsets[1:] - scene_offsets[:-1])[scene_of_chunk]                              # (B,)
+    u = torch.rand((scene_of_chunk.numel(), int(num_tries)), dtype=torch.float64, generator=generator, device=dev)
+    center_ind = torch.minimum((u * n[:, None]).long(), (n - 1).clamp_(min=0)[:, None]).contiguous()  # uniform on [0, n)
+    seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=generator, device=dev)
+    out = ops.sample_chunks(points, seg_label, scene_offsets, scene_of_chunk, center_ind, nb_pts, chunk_size=chunk_size,
+                            chunk_margin=chunk_margin, chunk_thresh=chunk_thresh, seed=seed, base_point_ind=base_point_ind,
+                            bounds_f64=bounds_f64)
+    out['center_ind'], out['seed'] = center_ind, seed
+    return out
+
+
 def _kinv_of(cam_matrix):
     """inverse of the 3x3 intrinsics in float32 on the host, as the loader does it (np.linalg.inv(cam_matrix[:3, :3]), scannet_2d3d.py:38)."""
     cam = cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)

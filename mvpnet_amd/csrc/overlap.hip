@@ -9,6 +9,7 @@
 //   select_frames_kernel  : `select_frames` (mvpnet/data/scannet_2d3d.py:20-30) for ALL chunks of a scene in one launch: one
 //                           workgroup per chunk, the still-uncovered base points as a bit row in LDS, one frame per lane,
 //                           score = sum of popcount(overlap row & uncovered), arg-max with the lowest frame index on ties.
+//                           <true>: a training batch -- every chunk with the frame rows of its own scene (mvp_select_frames_ranges_u32).
 //
 // Measurements: DESIGN.md (scene preparation).
 #include "unproject_core.h"
@@ -113,12 +114,33 @@ __global__ __launch_bounds__(T) void frame_overlap_kernel(const DepthT* __restri
 constexpr int kSelThreads = 256;
 constexpr int kSelMaxWords = 1024;  // 32768 base points
 
+// RANGED: chunk c chooses among rows [frame_begin[c], frame_begin[c] + frame_count[c]) of a matrix that holds several scenes' frames
+// (cut to [0, F); the lane's frame index is local to the range, so ties still go to the lowest row) and reports global rows.
+template <bool RANGED>
 __global__ __launch_bounds__(kSelThreads) void select_frames_kernel(const uint32_t* __restrict__ overlap,
                                                                    const uint32_t* __restrict__ chunk_bits, int F, int W, int n_pick,
+                                                                   const int64_t* __restrict__ frame_begin,
+                                                                   const int64_t* __restrict__ frame_count,
                                                                    int64_t* __restrict__ picked, int32_t* __restrict__ gain) {
   __shared__ uint32_t unc[kSelMaxWords];
   __shared__ unsigned long long wbest[kSelThreads / kWave];
   const int c = blockIdx.x, tid = threadIdx.x;
+  int64_t f0 = 0;
+  if (RANGED) {
+    f0 = frame_begin[c];
+    f0 = f0 < 0 ? 0 : (f0 > F ? F : f0);
+    int64_t cnt = frame_count[c];
+    cnt = cnt < 0 ? 0 : (cnt > F - f0 ? F - f0 : cnt);
+    F = (int)cnt;
+    overlap += (size_t)f0 * W;
+    if (F < 1) {  // (uniform over the workgroup) no frame to choose from: the caller's error, answered without reading a row
+      for (int pick = tid; pick < n_pick; pick += kSelThreads) {
+        picked[(size_t)c * n_pick + pick] = -1;
+        if (gain) gain[(size_t)c * n_pick + pick] = 0;
+      }
+      return;
+    }
+  }
   for (int j = tid; j < W; j += kSelThreads) unc[j] = chunk_bits[(size_t)c * W + j];
   __syncthreads();
   for (int pick = 0; pick < n_pick; ++pick) {
@@ -144,7 +166,7 @@ __global__ __launch_bounds__(kSelThreads) void select_frames_kernel(const uint32
     for (int i = 1; i < kSelThreads / kWave; ++i) key = wbest[i] > key ? wbest[i] : key;
     const int fb = (int)(~(unsigned)key);
     if (tid == 0) {
-      picked[(size_t)c * n_pick + pick] = fb;
+      picked[(size_t)c * n_pick + pick] = f0 + fb;
       if (gain) gain[(size_t)c * n_pick + pick] = (int32_t)(key >> 32);
     }
     const uint32_t* row = overlap + (size_t)fb * W;
@@ -207,7 +229,23 @@ MVP_API int mvp_select_frames_u32(const uint32_t* overlap_bits, const uint32_t* 
   MVP_REQUIRE(F >= 1 && F < (1ll << 31) && C >= 0 && C < (1ll << 31) && W >= 1 && n_pick >= 0 && n_pick < (1ll << 31));
   if (W > kSelMaxWords) return MVP_EUNSUPPORTED;
   if (C == 0 || n_pick == 0) return MVP_OK;
-  hipLaunchKernelGGL(select_frames_kernel, dim3((unsigned)C), dim3(kSelThreads), 0, static_cast<hipStream_t>(stream), overlap_bits,
-                     chunk_bits, (int)F, (int)W, (int)n_pick, picked, gain);
+  hipLaunchKernelGGL(select_frames_kernel<false>, dim3((unsigned)C), dim3(kSelThreads), 0, static_cast<hipStream_t>(stream), overlap_bits,
+                     chunk_bits, (int)F, (int)W, (int)n_pick, nullptr, nullptr, picked, gain);
+  return mvp_launch_status();
+}
+
+MVP_API int mvp_select_frames_ranges_u32(const uint32_t* overlap_bits, const uint32_t* chunk_bits, const int64_t* frame_begin,
+                                         const int64_t* frame_count, int64_t Ftot, int64_t C, int64_t W, int64_t n_pick, int64_t* picked,
+                                         int32_t* gain, mvp_stream_t stream) {
+  MVP_NONNULL(overlap_bits);
+  MVP_NONNULL(chunk_bits);
+  MVP_NONNULL(frame_begin);
+  MVP_NONNULL(frame_count);
+  MVP_NONNULL(picked);
+  MVP_REQUIRE(Ftot >= 1 && Ftot < (1ll << 31) && C >= 0 && C < (1ll << 31) && W >= 1 && n_pick >= 0 && n_pick < (1ll << 31));
+  if (W > kSelMaxWords) return MVP_EUNSUPPORTED;
+  if (C == 0 || n_pick == 0) return MVP_OK;
+  hipLaunchKernelGGL(select_frames_kernel<true>, dim3((unsigned)C), dim3(kSelThreads), 0, static_cast<hipStream_t>(stream), overlap_bits,
+                     chunk_bits, (int)Ftot, (int)W, (int)n_pick, frame_begin, frame_count, picked, gain);
   return mvp_launch_status();
 }

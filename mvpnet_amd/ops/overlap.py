@@ -64,12 +64,16 @@ def rgbd_overlap(depth, kinv, pose, base_points, radius=0.1, packed=False):
     return unpack_bits(bits, nb).t().contiguous()
 
 
-def select_frames_batched(overlap, chunk_base_mask, num_rgbd_frames, return_gain=False):
+def select_frames_batched(overlap, chunk_base_mask, num_rgbd_frames, return_gain=False, frame_begin=None, frame_count=None):
     """`select_frames` (scannet_2d3d.py:20-30) for all chunks of a scene in one launch; with bit rows as input there is no host
     synchronisation, bool input is packed first (pack_bits: one 8-byte constant copied to the device per matrix).
     overlap: bool (nb,F) (the reference's layout) or int32 (F,W) bit rows; chunk_base_mask: bool (C,nb) -- base point j lies in
     chunk c -- or int32 (C,W) bit rows.  -> picked (C,n) int64 [, gain (C,n) int32: newly covered base points per pick]; row c equals
-    select_frames(overlap[chunk_base_mask[c]], n)."""
+    select_frames(overlap[chunk_base_mask[c]], n).
+    frame_begin, frame_count (C,) int64 (both or neither): the chunks of a TRAINING batch, every chunk with the frames of its own
+    scene -- overlap then holds all scenes' frames one scene after the other, chunk c chooses among frames [begin, begin + count) only
+    and gets GLOBAL frame indices (mvp_select_frames_ranges_u32).  Device tensors are taken as they are (no synchronisation; count >= 1
+    and the range are then the caller's, a chunk without frames gets -1); host tensors or sequences are checked here first."""
     L.require_gpu(overlap, chunk_base_mask)
     if overlap.dim() != 2 or chunk_base_mask.dim() != 2:
         raise RuntimeError('select_frames_batched: overlap and chunk_base_mask must be 2-D')
@@ -89,5 +93,20 @@ def select_frames_batched(overlap, chunk_base_mask, num_rgbd_frames, return_gain
         raise RuntimeError('select_frames_batched: needs at least one frame and num_rgbd_frames >= 0')
     picked = torch.empty((C, n), dtype=torch.int64, device=ov.device)
     gain = torch.empty((C, n), dtype=torch.int32, device=ov.device) if return_gain else None
+    if (frame_begin is None) != (frame_count is None):
+        raise RuntimeError('select_frames_batched: frame_begin and frame_count go together')
+    if frame_begin is not None:
+        rng = []
+        for r in (frame_begin, frame_count):
+            r = torch.as_tensor(r)
+            if r.dtype != torch.int64 or r.shape != (C,):
+                raise RuntimeError('select_frames_batched: frame_begin and frame_count must be (C,) int64')
+            rng.append(r)
+        if not rng[0].is_cuda and not rng[1].is_cuda and C:  # host-known ranges: refused before anything is launched
+            if int(rng[1].min()) < 1 or int(rng[0].min()) < 0 or int((rng[0] + rng[1]).max()) > F:
+                raise RuntimeError('select_frames_batched: every chunk needs frame_count >= 1 and a range inside [0, {})'.format(F))
+        fb, fc = (r.to(ov.device).contiguous() for r in rng)
+        L.call('mvp_select_frames_ranges_u32', ov, L.ptr(ov), L.ptr(cb), L.ptr(fb), L.ptr(fc), F, C, W, n, L.ptr(picked), L.ptr(gain))
+        return (picked, gain) if return_gain else picked
     L.call('mvp_select_frames_u32', ov, L.ptr(ov), L.ptr(cb), F, C, W, n, L.ptr(picked), L.ptr(gain))
     return (picked, gain) if return_gain else picked

@@ -215,3 +215,42 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
                               'pixel_box': pixel_box[lo:hi].contiguous(), 'k': int(k)})
         lo = hi
     return chunk_batches, chunk_inds, n_pts
+
+
+def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2), chunk_thresh=0.3,
+                       num_tries=10, generator=None):
+    """One TRAINING batch from scenes resident on the device: what a batch of `ScanNet2D3DChunks.__getitem__` calls collates to
+    (mvpnet/data/scannet_2d3d.py:323-398 with get_rgbd_data's frame choice, :199-221), without a host synchronisation.
+    store: dict of device tensors --
+        points (Ntot,3) float32, seg_label (Ntot,) int64 (mapped, negative = unlabelled), scene_offsets (S+1,) int64: the scenes, one
+        after the other; base_point_ind (S,nbp) int64 inside each scene; overlap_bits (Ftot,W) int32 bit rows (ops.rgbd_overlap(...,
+        packed=True) per scene, concatenated) and frame_offsets (S+1,) int64; depth (Ftot,H,W), images (Ftot,3,H,W), pose (Ftot,4,4) at
+        the lifting resolution; cam / kinv (S,3,3) float32: every scene's intrinsics of that resolution and their inverse.
+    scene_of_chunk (B,) int64 on the device: the dataset indices of the batch.
+    chunks.sample_train_chunks draws the chunks (one call), ops.select_frames_batched with the scenes' frame ranges picks the frames
+    (one launch), the rest are gathers.  -> the dict MVPNet3D._forward and SegLoss read: images (B,nv,3,H,W), points (B,3,nb_pts),
+    seg_label (B,nb_pts), depth (B,nv,H,W), cam_matrix / kinv (B,nv,3,3), pose (B,nv,4,4), pixel_box (B,4) = chunk_box -/+ fl32(0.1) in
+    float32 (:274-281), k.  augment.DeviceAugmentation applies to it as to any batch."""
+    from . import chunks as CH
+    ch = CH.sample_train_chunks(store['points'], store['seg_label'], store['scene_offsets'], scene_of_chunk, nb_pts, chunk_size=chunk_size,
+                                chunk_margin=chunk_margin, chunk_thresh=chunk_thresh, num_tries=num_tries,
+                                base_point_ind=store['base_point_ind'], generator=generator)
+    return assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k)
+
+
+def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k):
+    """sample_train_batch behind the draw: `ch` is ops.sample_chunks' result for the store's scenes (with base_bits)."""
+    from . import ops
+    nv = int(num_rgbd_frames)
+    fo = store['frame_offsets']
+    begin = fo[scene_of_chunk]
+    count = fo[scene_of_chunk + 1] - begin
+    picked = ops.select_frames_batched(store['overlap_bits'], ch['base_bits'], nv, frame_begin=begin, frame_count=count)  # (B,nv) global rows
+    B = scene_of_chunk.numel()
+    box = ch['chunk_box']
+    return {'images': store['images'][picked].contiguous(), 'points': ch['points'], 'seg_label': ch['seg_label'],
+            'depth': store['depth'][picked].contiguous(),
+            'cam_matrix': store['cam'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
+            'kinv': store['kinv'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
+            'pose': store['pose'][picked].contiguous(),
+            'pixel_box': torch.cat([box[:, :2] - 0.1, box[:, 2:] + 0.1], dim=1), 'k': int(k)}
