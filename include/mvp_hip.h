@@ -72,7 +72,7 @@ int mvp_fps_checked_f32(const float* points, int64_t B, int64_t N, int64_t D, in
                         mvp_stream_t stream);
 int mvp_fps_debug_spin_limit(int polls);
 /* Which kernel family the LAST mvp_fps_* call of the calling thread launched -- the choice is made inside the library from the cloud's shape
- * (and the MVP_FPS_* lab switches), so tests assert it next to the oracle comparison: 0 none yet, 1 one sample per barrier
+ * (and the MVP_FPS_ROUNDS=0 baseline switch), so tests assert it next to the oracle comparison: 0 none yet, 1 one sample per barrier
  * (fps_kernel / fps_fast_kernel), 2 fps_rounds_kernel, 3 fps_stream_kernel (4097..8192 float32 points: the training step's sampler),
  * 4 fps_rounds_multi_kernel (several workgroups per cloud), 5 fps_global_kernel.  A test aid: thread-local, no device work. */
 int mvp_fps_last_kernel(void);

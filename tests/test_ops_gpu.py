@@ -95,7 +95,7 @@ def test_fps_vs_oracle(dev, B, N, M, D):
     idx = farthest_point_sample(g(pts, dev), M, transpose=False).cpu().numpy()
     np.testing.assert_array_equal(idx, O().fps(pts, M))
     # ... and it was the kernel this shape is meant to exercise (the library picks it from the shape: mvp_fps_last_kernel, include/mvp_hip.h).
-    # Under one of the MVP_FPS_* lab switches the choice is the switch's, not the default's: nothing to assert then.
+    # Under MVP_FPS_ROUNDS=0 (the one-sample baseline of the measurement scripts) the choice is the switch's: nothing to assert then.
     from mvpnet_amd import _lib as L
     if not any(k.startswith('MVP_FPS_') for k in os.environ):
         ran = L.lib().mvp_fps_last_kernel()
@@ -147,6 +147,25 @@ def test_fps_throughput_launch_shape(dev, kind):
     assert L.lib().mvp_set_fps_mode(0) == 0
     np.testing.assert_array_equal(got[:2].cpu().numpy(), O().fps(pts[:2], 512))
     np.testing.assert_array_equal(got5[7:].cpu().numpy(), O().fps(pts[7:, :5000], 300))
+
+
+def test_fps_throughput_shape_beyond_the_stream_kernel(dev):
+    """shape=1, eight clouds, 7500 -> 7500: about the smallest cloud whose stream kernel does not fit the LDS (16 N + 4 M + 10832 bytes
+    with M <= N pass its 159744-byte limit from N = 7446; here 160848), so the narrow shape of fps_rounds_kernel -- 512 threads, 16 points
+    per lane -- takes the call; no other test reaches that instantiation.  Same indices as the default shape on all clouds and as the
+    oracle on two of them, the second with every point twice."""
+    from mvpnet_amd import _lib as L
+    from mvpnet_amd.ops import farthest_point_sample
+    N = M = 7500
+    pts = np.random.RandomState(7500).rand(8, N, 3).astype(np.float32)
+    pts[1, N // 2:] = pts[1, :N - N // 2]
+    x = g(pts, dev)
+    got = farthest_point_sample(x, M, transpose=False, shape=1)
+    ran = L.lib().mvp_fps_last_kernel()
+    assert torch.equal(got, farthest_point_sample(x, M, transpose=False, shape=0))
+    np.testing.assert_array_equal(got[:2].cpu().numpy(), O().fps(pts[:2], M))
+    if not any(k.startswith('MVP_FPS_') for k in os.environ):
+        assert ran == 2, 'kernel family {} ran, 2 (rounds) expected'.format(ran)
 
 
 def test_fps_f64_vs_oracle(dev):
@@ -2306,7 +2325,7 @@ def test_fps_rounds_across_workgroups(dev, B, N, M, D):
     """Clouds of 8193..65536 points: four workgroups per cloud run the round protocol together and exchange their row results through
     device-scope atomics (fps_rounds_multi_kernel) -- the dense configuration's 32768 -> 8192 level at full size among the cases.  Same
     indices as the oracle; the same again while the split-bf16 MLP kernels keep the rest of the chip busy (the exchange must not
-    depend on when a partner workgroup gets to run); and as the one-sample kernels (MVP_FPS_MULTI=0 is the library's A/B switch, read
+    depend on when a partner workgroup gets to run); and as the one-sample kernels (MVP_FPS_ROUNDS=0 is the library's baseline switch, read
     once per process, so that comparison lives in tools/exp/fps_multi_time.py)."""
     from mvpnet_amd import ops, _lib as L
     rs = np.random.RandomState(N + M)

@@ -1,4 +1,4 @@
-"""Sampling of clouds beyond 8192 points: rounds across 4 workgroups per cloud vs the one-sample kernels (MVP_FPS_MULTI=0)."""
+"""Sampling of clouds beyond 8192 points: rounds across 4 workgroups per cloud vs the one-sample kernels (MVP_FPS_ROUNDS=0)."""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
