@@ -363,6 +363,50 @@ int mvp_sample_chunks_f32(const float* points, const int64_t* seg_label, const i
                           float* out_points, int64_t* out_label, float* chunk_box, int32_t* try_index, int32_t* num_members,
                           uint32_t* base_bits, void* workspace, int64_t workspace_bytes, mvp_stream_t stream);
 
+/* ---- ragged scenes: the whole-scene chunker and the packing of its chunks (NEW on the device) ----
+ * scene2chunks_legacy (mvpnet/utils/chunk_util.py:4-53) for all sliding windows of a scene, as index lists in CSR form instead of
+ * (windows x points) membership matrices.  points (n,3) float32; corners (nc,2) float32: the windows' lower xy corners, computed by the
+ * caller from the scene's extent (float32: `coord_min + float32(i * stride)`); size, margin: the Python floats, as doubles.
+ * The rule, pinned (the arithmetic of the reference under NumPy 2: float32 + Python float stays float32, corner + ndarray(float64) is
+ * float64), per axis a in {x, y}, nothing contracted:
+ *   inner: p.a >= lo.a in float32  &&  (double)p.a <= (double)lo.a + size.a
+ *   outer: (double)p.a >= (double)lo.a - margin.a  &&  (double)p.a <= ((double)lo.a + size.a) + margin.a
+ *   a NaN coordinate is never a member (every comparison is false); z takes no part.
+ * mvp_scene_chunks_count_f32: inner_count[w], outer_count[w] (nc,) int32 for every window, one pass.  The caller reads them back --
+ *   batch shapes are host values --, keeps the windows with inner_count >= thresh (chunk_util.py:33-36) and forms
+ *   kept (C,) int32 window ids, ascending, and offsets (C+1,) int64, the exclusive sums of their outer counts, both on the device.
+ * mvp_scene_chunks_fill_f32: for kept window c
+ *   index[offsets[c] .. offsets[c+1]) = its members by the outer test, in ASCENDING point index (int64; `total` = elements of index);
+ *   zbox[c] = (min z, max z) over them, float32, NaN-propagating like torch.amin / amax; (+inf, -inf) for an empty list;
+ *   base_bits (C,ceil(nb/32)) uint32 when nb > 0: bit j % 32 of word j / 32 = base point base_point_ind[j] ((nb,) int64) is a member
+ *   (the rows mvp_select_frames_u32 reads; padding bits zero).  base_point_ind NULL with nb = 0.
+ * Index arrays' contents are the caller's: kept and base_point_ind values are clamped into their ranges, a slice of offsets is cut to
+ * [0, total] and a list longer than its slice loses its tail (a wrong result, never a stray access).
+ * Limits: n < 2^31, nc and C <= MVP_CHUNKER_MAX_WINDOWS, nb <= MVP_OVERLAP_MAX_BASE: MVP_EUNSUPPORTED beyond, nothing is launched.
+ * MVP_EINVAL unless n, nc >= 1, C, nb, total >= 0 and no NaN among size / margin.  Integer counts and ordered lists: bit-reproducible. */
+#define MVP_CHUNKER_MAX_WINDOWS 65535
+int mvp_scene_chunks_count_f32(const float* points, int64_t n, const float* corners, int64_t nc, double size_x, double size_y,
+                               double margin_x, double margin_y, int32_t* inner_count, int32_t* outer_count, mvp_stream_t stream);
+int mvp_scene_chunks_fill_f32(const float* points, int64_t n, const float* corners, int64_t nc, double size_x, double size_y,
+                              double margin_x, double margin_y, const int32_t* kept, const int64_t* offsets, int64_t C,
+                              const int64_t* base_point_ind, int64_t nb, int64_t* index, int64_t total, float* zbox, uint32_t* base_bits,
+                              mvp_stream_t stream);
+
+/* All chunks of a scene written as padded coordinate rows in one launch: chunk c, with n_c = offsets[c+1] - offsets[c] members
+ * index[offsets[c] ..), becomes the (3, N_c) float32 matrix at out + out_base[c], N_c = out_len[c] (offsets (C+1,), out_base, out_len
+ * (C,) int64 on the device; out_base in floats) -- chunks of one N_c laid one after the other are a (B,3,N_c) batch.
+ *   slot s < n_c  takes points[index[offsets[c] + s]];
+ *   slot s >= n_c takes member ((uint64)h(s ^ s_c ^ 0x85EBCA6B) * n_c) >> 32, s_c = h(seed32 + 0x9E3779B9 * (c+1)), h = lowbias32 and
+ *   seed32 = low ^ high word of the seed: the pad rule of mvp_sample_chunks_f32 -- uniform duplicates of the chunk's own points BEHIND the
+ *   originals, the law of mvpnet/test_mvpnet_3d.py:146-154, not its draws.
+ * host_lengths, host_out_len (C,) int64 ON THE HOST: n_c and N_c once more (the launch shape needs the widest chunk; the caller holds
+ * both): MVP_EINVAL unless N_c >= n_c >= 1 for every chunk.  The device arrays' contents are the caller's: point indices are clamped
+ * into [0, n), a chunk whose rows would leave [out, out + out_floats) or whose slice of index is empty is not written at all.
+ * n < 2^31, C <= MVP_CHUNKER_MAX_WINDOWS, N_c < 2^31: MVP_EUNSUPPORTED beyond. */
+int mvp_pack_chunks_f32(const float* points, int64_t n, const int64_t* index, int64_t total, const int64_t* offsets, int64_t C,
+                        const int64_t* out_base, const int64_t* out_len, const int64_t* host_lengths, const int64_t* host_out_len,
+                        uint64_t seed, float* out, int64_t out_floats, mvp_stream_t stream);
+
 /* Column slices of several row-major float matrices in one launch (host-side helper of the shared-MLP path: the reference slices
  * nothing -- it concatenates the inputs instead, modules.py:32-35,178-186 -- the linear-first factorisation of those layers needs
  * each column group of the weight as its own aligned operand).  table: n x 6 int64 ON THE DEVICE, per entry

@@ -138,6 +138,9 @@ _SIGNATURES = {
     'mvp_select_frames_u32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
     'mvp_select_frames_ranges_u32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
     'mvp_sample_chunks_f32': [_ptr] * 6 + [_i64] * 6 + [ctypes.c_double] * 5 + [ctypes.c_int, ctypes.c_uint64] + [_ptr] * 9 + [_i64, _ptr],
+    'mvp_scene_chunks_count_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _ptr],
+    'mvp_scene_chunks_fill_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr],
+    'mvp_pack_chunks_f32': [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _ptr, _i64, _ptr],
 }
 # the shared-MLP entry points with the precision as arguments (csrc/mlp_prec.hip): base parameters + (precision, precision_backward)
 for _n in ['mvp_mlp_forward_f32', 'mvp_mlp_forward_bn_f32', 'mvp_mlp_forward_rel_bn_f32', 'mvp_mlp_forward_pool_f32', 'mvp_mlp_input_grad_f32', 'mvp_mlp_input_grad_dropout_f32',

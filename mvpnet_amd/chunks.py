@@ -10,18 +10,23 @@ import numpy as np
 import torch
 
 
+def _window_corners(points, chunk_size, stride):
+    """(nc,2) float32 lower xy corners of the sliding windows, on the host (chunk_util.py:20-30)."""
+    ext = torch.stack([points.min(0).values, points.max(0).values]).cpu().numpy()  # (2,3) float32, the one scalar round trip
+    coord_min, coord_max = ext[0], ext[1]
+    limit = coord_max - coord_min
+    num_chunks = np.ceil((limit[:2] - chunk_size) / stride).astype(int) + 1
+    return np.array([(coord_min[0] + np.float32(i * stride), coord_min[1] + np.float32(j * stride))
+                     for i in range(num_chunks[0]) for j in range(num_chunks[1])], np.float32).reshape(-1, 2)
+
+
 def scene2chunks_legacy(points, chunk_size, stride, thresh=1000, margin=(0.2, 0.2), return_bbox=False):
     """points (n,3) float32 tensor (any device) -> list of int64 index tensors [, list of (6,) float64 bboxes x1,y1,z1,x2,y2,z2]."""
     assert points.dim() == 2 and points.size(1) == 3 and points.dtype == torch.float32
     dev = points.device
     chunk_size = np.asarray(chunk_size, np.float64)
     margin_np = np.asarray(margin, np.float64)
-    ext = torch.stack([points.min(0).values, points.max(0).values]).cpu().numpy()  # (2,3) float32, the one scalar round trip
-    coord_min, coord_max = ext[0], ext[1]
-    limit = coord_max - coord_min
-    num_chunks = np.ceil((limit[:2] - chunk_size) / stride).astype(int) + 1
-    corners = np.array([(coord_min[0] + np.float32(i * stride), coord_min[1] + np.float32(j * stride))
-                        for i in range(num_chunks[0]) for j in range(num_chunks[1])], np.float32).reshape(-1, 2)
+    corners = _window_corners(points, chunk_size, stride)
     if corners.shape[0] == 0:
         return ([], []) if return_bbox else []
     lo = torch.from_numpy(corners).to(dev)                                       # (nc,2) float32
@@ -45,6 +50,41 @@ def scene2chunks_legacy(points, chunk_size, stride, thresh=1000, margin=(0.2, 0.
     lo_k, hi_k = lo.double()[keep] - mg, hi[keep] + mg
     boxes = torch.cat([lo_k, zmin[:, None], hi_k, zmax[:, None]], dim=1)
     return chunk_indices, list(boxes)
+
+
+def scene2chunks_csr(points, chunk_size, stride, thresh=1000, margin=(0.2, 0.2), base_point_ind=None):
+    """scene2chunks_legacy's chunks as ONE flat index list: no (windows x points) matrices, no per-chunk tensors, and with
+    `base_point_ind` ((nb,) int64) the chunks' base-point bit rows for ops.select_frames_batched.  Two host round trips: the scene's
+    extent, and the windows' point counts (ops.scene_chunks).
+    -> dict: offsets (C+1,) int64 and index (total,) int64 on the points' device -- chunk c is index[offsets[c]:offsets[c+1]], ascending
+    --, lengths: list of C ints, boxes (C,6) float64 x1,y1,z1,x2,y2,z2 as `scene2chunks_legacy(..., return_bbox=True)`, base_bits
+    (C,ceil(nb/32)) int32 or None.  Same lists, bit for bit, as scene2chunks_legacy -- which is also what builds the dict for a CPU tensor
+    and for a scene beyond the kernel's limits (2^31 points, 65535 windows, 4096 base points)."""
+    from . import ops
+    assert points.dim() == 2 and points.size(1) == 3 and points.dtype == torch.float32
+    dev = points.device
+    nb = 0 if base_point_ind is None else int(base_point_ind.numel())
+    size_np, margin_np = np.asarray(chunk_size, np.float64), np.asarray(margin, np.float64)
+    corners = _window_corners(points, size_np, stride)
+    if not (points.is_cuda and ops.chunker.supported(points.size(0), corners.shape[0], nb)):
+        idx, boxes = scene2chunks_legacy(points, chunk_size, stride, thresh=thresh, margin=margin, return_bbox=True)
+        lengths = [int(i.numel()) for i in idx]
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
+        bits = None
+        if nb:
+            member = torch.zeros((len(idx), points.size(0)), dtype=torch.bool, device=dev)
+            for c, i in enumerate(idx):
+                member[c, i] = True
+            bits = ops.pack_bits(member[:, base_point_ind.to(dev)])
+        return {'offsets': offsets, 'index': torch.cat(idx) if idx else torch.zeros(0, dtype=torch.int64, device=dev), 'lengths': lengths,
+                'boxes': torch.stack(boxes) if boxes else torch.zeros((0, 6), dtype=torch.float64, device=dev), 'base_bits': bits}
+    lo = torch.from_numpy(corners).to(dev)
+    ch = ops.scene_chunks(points, lo, size_np, margin_np, thresh, base_point_ind=base_point_ind)
+    lo_k = lo.double()[torch.from_numpy(ch['kept']).to(dev)]  # the arithmetic of scene2chunks_legacy's boxes, for the kept windows only
+    mg = torch.from_numpy(margin_np).to(dev)
+    z = ch['zbox'].double()
+    boxes = torch.cat([lo_k - mg, z[:, :1], (lo_k + torch.from_numpy(size_np).to(dev)) + mg, z[:, 1:]], dim=1)
+    return {'offsets': ch['offsets'], 'index': ch['index'], 'lengths': ch['lengths'], 'boxes': boxes, 'base_bits': ch['base_bits']}
 
 
 def select_frames(rgbd_overlap, num_rgbd_frames):
@@ -97,11 +137,12 @@ def _kinv_of(cam_matrix):
     return np.linalg.inv(cam.astype(np.float32)[..., :3, :3])
 
 
-def compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=2000, radius=0.1, generator=None):
+def compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=2000, radius=0.1, generator=None, packed=False):
     """`compute_rgbd_knn` (mvpnet/data/preprocess/preprocess.py:99-170) on the device: the two arrays the reference stores per scene.
     points (n,3) float32 device tensor (the whole scene), depth (F,h,w) float32 metres or (u)int16 millimetres, cam_matrix (3,3) or
     (4,4) intrinsics OF THE DEPTH MAPS' RESOLUTION (array or tensor; (F,3,3) for per-frame intrinsics), pose (F,4,4) float32.
-    -> base_point_ind (num_base_pts,) int64, overlaps (num_base_pts, F) bool  (`base_point_ind`, `pointwise_rgbd_overlap`).
+    -> base_point_ind (num_base_pts,) int64, overlaps (num_base_pts, F) bool  (`base_point_ind`, `pointwise_rgbd_overlap`); with
+    packed=True the overlaps stay the kernel's int32 (F, ceil(num_base_pts/32)) bit rows, as ops.select_frames_batched reads them.
 
     Base points are `randperm(n)[:num_base_pts]` from `generator` (or torch's global generator of the device): the same LAW as the
     reference's `np.random.choice(n, num_base_pts, replace=False)`, not the same draws.
@@ -120,5 +161,6 @@ def compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=2000, rad
     kinv = torch.from_numpy(np.ascontiguousarray(_kinv_of(cam_matrix))).to(points.device)
     if kinv.dim() == 2:
         kinv = kinv.expand(F, 3, 3)
-    overlaps = ops.rgbd_overlap(depth.contiguous(), kinv.contiguous(), pose.contiguous(), points[base_point_ind].contiguous(), radius=radius)
+    overlaps = ops.rgbd_overlap(depth.contiguous(), kinv.contiguous(), pose.contiguous(), points[base_point_ind].contiguous(), radius=radius,
+                                packed=packed)
     return base_point_ind, overlaps

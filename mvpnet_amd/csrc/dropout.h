@@ -5,6 +5,12 @@
 
 namespace {
 
+// lowbias32: a bijection of 32-bit words; the counter hash of the dropout mask and of the chunk resampling (sample.hip, chunker.hip)
+__host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+
 // Dropout folded into the BatchNorm + ReLU passes of a layer (SharedMLPDO, mlp.py:86-92: dropout behind the layer): the keep mask is a
 // counter-based hash of (seed, element index), so forward and backward regenerate it instead of storing it -- no mask tensor, no
 // fused_dropout / masked_scale launches.  (The reference draws its mask from torch's Philox stream: the masks differ, the
@@ -14,9 +20,7 @@ struct Dropout {
   unsigned seed;
   float scale;      // 1 / (1 - p)
   __device__ __forceinline__ float factor(unsigned e) const {  // e = r * C + c
-    unsigned x = e + seed * 0x9E3779B9u;
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;  // lowbias32
-    return x >= thresh ? scale : 0.f;
+    return lowbias32(e + seed * 0x9E3779B9u) >= thresh ? scale : 0.f;
   }
 };
 

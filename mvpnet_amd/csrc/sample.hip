@@ -17,7 +17,7 @@
 //   finish_kernel  : one workgroup per chunk: bitonic sort of the pairs in LDS (crop) or the pad rule, then the gather of points and
 //                    labels and the base-point bits.
 // Measurements: DESIGN.md (training chunks).
-#include "common.h"
+#include "dropout.h"  // lowbias32
 #include <math.h>
 
 namespace {
@@ -29,11 +29,6 @@ constexpr int kSmpMaxPts = MVP_SAMPLE_MAX_PTS;  // 8192 (key, index) pairs = 64 
 constexpr int kFinThreads = 1024;
 constexpr int kBins0 = 256, kBins12 = 4096;
 constexpr int kHistWords = kBins0 + 2 * kBins12;
-
-__host__ __device__ inline uint32_t lowbias32(uint32_t x) {  // dropout.h's hash: a bijection of 32-bit words
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
 
 struct ChunkState {  // per chunk, written by pick_kernel
   double lo_x, lo_y, hi_x, hi_y;  // the winning box (float32 bounds are exact in double, so later passes compare in double only)

@@ -31,7 +31,8 @@ def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_cl
     chunk_batches: list of data dicts (the reference's keys, tensors on the device) holding THIS RANK's chunks in the order
         `dist.shard_chunks(num_chunks, rank, world)`, any batch sizes.  Chunks may have DIFFERENT numbers of points (the
         reference feeds every chunk with all its points, `nb_pts=-1`, padded to >= 2048: pad_sparse_chunk): every batch holds
-        chunks of one size (a ragged scene is simply passed as batches of 1, or grouped by size); a rank may hold none.
+        chunks of one size (a ragged scene is simply passed as batches of 1, or grouped by size: prepare_scene_bucketed pads
+        chunks of similar size to a common one); a rank may hold none.
     chunk_inds: list over ALL chunks (global order) of int64 tensors on the device: scene point ids of each chunk's points;
         `len(chunk_inds[i]) <= N_i`, logits beyond it belong to padded points and are ignored (test_mvpnet_3d.py:160-164).
     n_pts: number of scene points.
@@ -174,7 +175,6 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
     `min_nb_pts` by pad_sparse_chunk; consecutive chunks of equal size share a batch of up to `batch_size`, the chunk order is kept.
     -> (chunk_batches, chunk_inds, n_pts) with the keys MVPNet3D._forward reads: images (B,nv,3,H,W), points (B,3,N), depth (B,nv,H,W),
     cam_matrix / kinv (B,nv,3,3), pose (B,nv,4,4), pixel_box (B,4) = chunk box -/+ 0.1 m (:274-281), k."""
-    import numpy as np
     from . import chunks as CH
     from . import ops
     dev = points.device
@@ -190,16 +190,7 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
     picked = ops.select_frames_batched(overlaps if overlaps.dtype == torch.int32 else overlaps.bool(),
                                        chunk_base_masks(chunk_inds, base_point_ind, n_pts), num_rgbd_frames)  # (C,nv)
 
-    ldepth = depth if lift_depth is None else lift_depth
-    F, H, W = ldepth.shape
-    if images.shape[0] != F or tuple(images.shape[-2:]) != (H, W):
-        raise RuntimeError('prepare_scene: images (F,3,H,W) and the lifting depth (F,H,W) disagree: pass lift_depth at the images\' resolution')
-    cam = (cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)).astype(np.float32)[..., :3, :3].copy()
-    cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
-    cam[..., 1, :] /= np.float32(depth.size(1) / H)
-    kinv = np.linalg.inv(cam)  # float32, :38
-    cam_t = torch.from_numpy(cam).to(dev).expand(F, 3, 3)
-    kinv_t = torch.from_numpy(np.ascontiguousarray(kinv)).to(dev).expand(F, 3, 3)
+    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene')
     box = torch.stack(boxes)[:, [0, 1, 3, 4]]  # (C,4) float64 x1,y1,x2,y2
     pixel_box = (box + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=box.device)).float().to(dev)
 
@@ -209,12 +200,121 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
         hi = lo + 1
         while hi < len(singles) and hi - lo < batch_size and singles[hi].size(1) == singles[lo].size(1):
             hi += 1
-        sel = picked[lo:hi]  # (B,nv)
-        chunk_batches.append({'images': images[sel].contiguous(), 'points': torch.stack(singles[lo:hi]).contiguous(), 'depth': ldepth[sel].contiguous(),
-                              'cam_matrix': cam_t[sel].contiguous(), 'kinv': kinv_t[sel].contiguous(), 'pose': pose[sel].contiguous(),
-                              'pixel_box': pixel_box[lo:hi].contiguous(), 'k': int(k)})
+        chunk_batches.append(_chunk_batch(fr, picked[lo:hi], torch.stack(singles[lo:hi]).contiguous(), pixel_box[lo:hi], k))
         lo = hi
     return chunk_batches, chunk_inds, n_pts
+
+
+def _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, who):
+    """What every batch of a scene gathers its frames from: the lifting-resolution depth maps and the intrinsics scaled to them with
+    their inverse (scannet_2d3d.py:206-210, :38), per frame, on the device."""
+    import numpy as np
+    ldepth = depth if lift_depth is None else lift_depth
+    F, H, W = ldepth.shape
+    if images.shape[0] != F or tuple(images.shape[-2:]) != (H, W):
+        raise RuntimeError(who + ': images (F,3,H,W) and the lifting depth (F,H,W) disagree: pass lift_depth at the images\' resolution')
+    cam = (cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)).astype(np.float32)[..., :3, :3].copy()
+    cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
+    cam[..., 1, :] /= np.float32(depth.size(1) / H)
+    kinv = np.linalg.inv(cam)  # float32, :38
+    return {'images': images, 'depth': ldepth, 'pose': pose, 'cam_matrix': torch.from_numpy(cam).to(dev).expand(F, 3, 3),
+            'kinv': torch.from_numpy(np.ascontiguousarray(kinv)).to(dev).expand(F, 3, 3)}
+
+
+def _chunk_batch(fr, sel, points, pixel_box, k):
+    """One batch: the frames `sel` (B,nv) of `_frame_tensors`' dict beside the chunks' points (B,3,N) and pixel boxes (B,4)."""
+    return {'images': fr['images'][sel].contiguous(), 'points': points, 'depth': fr['depth'][sel].contiguous(),
+            'cam_matrix': fr['cam_matrix'][sel].contiguous(), 'kinv': fr['kinv'][sel].contiguous(), 'pose': fr['pose'][sel].contiguous(),
+            'pixel_box': pixel_box.contiguous(), 'k': int(k)}
+
+
+def bucket_size(n, min_nb_pts, max_bucket):
+    """The padded size of a chunk of n points: the smallest rung >= max(n, min_nb_pts) of the ladder min_nb_pts x {1, 1.5, 2, 3, 4, 6, 8,
+    12, 16, ...} (1.5 x rounded down; consecutive rungs differ by <= 1.5 x for min_nb_pts >= 2, so a chunk is padded to less than
+    1.5 x max(n, min_nb_pts) rows), but never beyond max_bucket; a chunk above max_bucket keeps its size."""
+    n, m = int(n), int(min_nb_pts)
+    need = max(n, m)
+    if n > max_bucket or m < 1:
+        return need
+    rung = m
+    while rung < need:
+        half = rung * 3 // 2
+        rung = half if half >= need else rung * 2
+    return max(need, min(rung, int(max_bucket)))
+
+
+def plan_buckets(lengths, min_nb_pts=2048, batch_size=32, max_batch_points=32 * 8192, max_bucket=32768):
+    """Batches for chunks of `lengths` points: every chunk is padded to bucket_size(n), the chunks are sorted by that size (ties keep
+    their order) and cut into batches of at most min(batch_size, max(1, max_batch_points // size)) chunks of one size; a chunk above
+    max_bucket is a batch of its own.  Host arithmetic only.  -> (batches: list of (size, [chunk numbers]), order: the chunk numbers in
+    the batches' order)."""
+    sizes = [bucket_size(n, min_nb_pts, max_bucket) for n in lengths]
+    order = sorted(range(len(sizes)), key=lambda c: sizes[c])  # (stable)
+    batches = []
+    for c in order:
+        N = sizes[c]
+        cap = 1 if lengths[c] > max_bucket else min(int(batch_size), max(1, int(max_batch_points) // N))
+        if batches and batches[-1][0] == N and len(batches[-1][1]) < cap and lengths[batches[-1][1][0]] <= max_bucket:
+            batches[-1][1].append(c)
+        else:
+            batches.append((N, [c]))
+    return batches, order
+
+
+def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
+                           min_nb_pts=2048, overlap=None, batch_size=32, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None,
+                           pad_seed=0, max_batch_points=32 * 8192, max_bucket=32768):
+    """prepare_scene for a scene whose chunks have DIFFERENT sizes (the reference's test loop feeds every chunk with all its points):
+    chunks of similar size share a batch after being padded to a common size (plan_buckets), with no per-chunk work on the host.
+    Arguments as prepare_scene, `pad_seed` (an int) in place of `pad_generator`; single process.
+
+    Padding is exact in eval mode: the duplicates are appended BEHIND a chunk's own points, so farthest point sampling picks the same
+    indices (lowest index on ties), every ball holds the same distinct points, and the padded columns' logits are dropped by the vote.
+    Steps: chunks.scene2chunks_csr (two kernels; the second and last device-to-host read of the preparation is the windows' counts),
+    ops.pack_chunks (one launch writes every batch's points; the batches are views of one buffer), ONE ops.select_frames_batched call on
+    bit rows (the overlap's and the chunker's base_bits: no membership matrix), then the frame gathers of prepare_scene.
+    -> (chunk_batches, chunk_inds, n_pts, order): the batches sorted by size, chunk_inds -- views of the flat index list -- in THE
+    BATCHES' ORDER, so `infer_scene(model, chunk_batches, chunk_inds, n_pts)` works as it stands; order[i] = the chunker's number
+    (scene2chunks_legacy's position) of the i-th chunk.  The vote adds a point's logits in this order, not in the chunker's: sums differ
+    from prepare_scene's in the last bits only."""
+    from . import chunks as CH
+    from . import ops
+    dev = points.device
+    n_pts = points.size(0)
+    if overlap is None:
+        base_point_ind, ov = CH.compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=num_base_pts, radius=radius, generator=generator,
+                                                     packed=True)
+    else:
+        base_point_ind, ov = overlap
+        base_point_ind = torch.as_tensor(base_point_ind).to(dev).long()
+        ov = torch.as_tensor(ov).to(dev)
+        ov = ov if ov.dtype == torch.int32 else ops.pack_bits(ov.bool().t())
+    csr = CH.scene2chunks_csr(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin, base_point_ind=base_point_ind.contiguous())
+    lengths = csr['lengths']
+    if not lengths:
+        return [], [], n_pts, []
+    if min(lengths) < 1:
+        raise RuntimeError('prepare_scene_bucketed: a chunk without points (chunk_thresh must be at least 1)')
+    batches, order = plan_buckets(lengths, min_nb_pts=min_nb_pts, batch_size=batch_size, max_batch_points=max_batch_points, max_bucket=max_bucket)
+    out_base, out_len, at = [0] * len(lengths), [0] * len(lengths), 0
+    for N, members in batches:
+        for c in members:
+            out_base[c], out_len[c], at = at, N, at + 3 * N
+    packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len, seed=pad_seed)
+    picked = ops.select_frames_batched(ov, csr['base_bits'], num_rgbd_frames)  # (C,nv), the chunker's order
+    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed')
+    pixel_box = (csr['boxes'][:, [0, 1, 3, 4]] + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=dev)).float()
+    order_t = torch.tensor(order, dtype=torch.int64).to(dev)
+    picked, pixel_box = picked[order_t], pixel_box[order_t]
+    chunk_batches, lo = [], 0
+    for N, members in batches:
+        hi, first = lo + len(members), out_base[members[0]]
+        chunk_batches.append(_chunk_batch(fr, picked[lo:hi], packed[first:first + len(members) * 3 * N].view(len(members), 3, N), pixel_box[lo:hi], k))
+        lo = hi
+    offs = [0]
+    for n in lengths:
+        offs.append(offs[-1] + n)
+    return chunk_batches, [csr['index'][offs[c]:offs[c + 1]] for c in order], n_pts, order
 
 
 def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2), chunk_thresh=0.3,
