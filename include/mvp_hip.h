@@ -27,6 +27,7 @@
 #ifndef MVP_HIP_H_
 #define MVP_HIP_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -406,6 +407,36 @@ int mvp_scene_chunks_fill_f32(const float* points, int64_t n, const float* corne
 int mvp_pack_chunks_f32(const float* points, int64_t n, const int64_t* index, int64_t total, const int64_t* offsets, int64_t C,
                         const int64_t* out_base, const int64_t* out_len, const int64_t* host_lengths, const int64_t* host_out_len,
                         uint64_t seed, float* out, int64_t out_floats, mvp_stream_t stream);
+
+/* ---- frames (NEW on the device; the reference prepares every frame in a data-loader worker) ----
+ * The picked frames of a raw uint8 store as the 2D network reads them: T.ColorJitter(brightness, contrast, saturation) on the PIL
+ * image, `/ 255.`, `(image - mean) / std`, np.fliplr (mvpnet/data/scannet_2d3d.py:241-252, :293-296; mvpnet/data/scannet_2d.py:158-171).
+ *   frames (Ftot,H,W,3) uint8 RGB as a PNG decodes; picked (Nf,) int64 global rows, clamped to [0, Ftot) (the contents of an index
+ *   array are the caller's: a wrong frame, never a stray read); factor (Nf,3) float32 = (brightness, contrast, saturation) and order
+ *   (Nf,3) uint8, both or neither (NULL: no jitter); flip (Nf,) uint8 or NULL; mean_std: 6 float32 ON THE DEVICE (mean rgb, std rgb)
+ *   or NULL; -> out (Nf,3,H,W) float32, or (Nf,H,W,3) when channels_last != 0.
+ * Pinned definition -- for given factors and order bit-identical to PIL's ImageEnhance.{Brightness,Contrast,Color}(img).enhance(f)
+ * chain (what torchvision's PIL path calls); every step maps uint8 RGB to uint8 RGB:
+ *   gray(r,g,b) = (r*19595 + g*38470 + b*7471 + 0x8000) >> 16                                  (PIL's convert('L'))
+ *   blend(d,p,f): t = fl32(fl32(d) + fl32(f * fl32(p - d))), p - d the integer difference, nothing contracted;
+ *                 0 if t <= 0, 255 if t >= 255, else (uint8)(int)t  (for 0 <= f <= 1, where PIL does not clip, t lies in [0, 255])
+ *   brightness: channel = blend(0, channel, f);  saturation: blend(gray(pixel), channel, f);  contrast: blend(m, channel, f) with
+ *   m = (2*S + n) / (2*n) in integers, S = the sum of gray over the n = H*W pixels of the image AS IT ENTERS this step
+ *   (PIL: int(S / n + 0.5) in double -- the same number for every size this entry takes).
+ *   order[i] = the op applied i-th: 0 brightness, 1 contrast, 2 saturation, any other value = no step; a second contrast code is
+ *   skipped too (one mean per frame).  A factor of exactly 1 leaves the image unchanged (t = p).
+ *   value: v = fl32(fl32(u) / 255.f); with mean_std fl32(fl32(v - mean[c]) / std[c]) -- IEEE float32 divisions, NumPy's arithmetic.
+ *   flip[i] != 0: output column x holds input column W-1-x, after everything else (the contrast mean does not depend on it).
+ * Any alignment is accepted: with W % 4 == 0, frames 4-byte and out 16-byte aligned a lane handles four pixels with wide loads and
+ * stores, otherwise one pixel; the results are the same.
+ * Two launches behind one hipMemsetAsync of the workspace (the frames' grey sums, integer atomics: bit-reproducible), one launch without
+ * a jitter; no allocation, no synchronisation (graph-capturable).  workspace: mvp_prepare_frames_workspace(Nf) bytes, 8-byte aligned;
+ * needed with a jitter only.  Frame bases are 64-bit (a store may exceed 4 GiB), offsets inside a frame 32-bit.
+ * MVP_EINVAL for Ftot, H, W or Nf < 1 or exactly one of factor / order NULL; MVP_EUNSUPPORTED for H*W*3 >= 2^31. */
+size_t mvp_prepare_frames_workspace(int64_t Nf);
+int mvp_prepare_frames_u8(const uint8_t* frames, int64_t Ftot, int64_t H, int64_t W, const int64_t* picked, int64_t Nf, const float* factor,
+                          const uint8_t* order, const uint8_t* flip, const float* mean_std, int channels_last, float* out, void* workspace,
+                          mvp_stream_t stream);
 
 /* Column slices of several row-major float matrices in one launch (host-side helper of the shared-MLP path: the reference slices
  * nothing -- it concatenates the inputs instead, modules.py:32-35,178-186 -- the linear-first factorisation of those layers needs

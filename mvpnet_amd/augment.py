@@ -5,8 +5,11 @@ instead of loader-computed `knn_indices` / `image_xyz`).
 The random DRAWS stay on the host, as in the reference (numpy RNG: one `rand()` per view for the flip, one `uniform(lo, hi)`
 angle per chunk); what they select is applied by the HIP kernels where the reference applies it: the flip changes the flat
 pixel ids / feature rows (mvp_lift_aug_f32), the rotation acts on `points` and the gathered `image_xyz` after the k-NN search
-(float64 product, one rounding to float32 -- scipy's Rotation.apply).  `color_jitter` is an image-space PIL transform of the
-loader and is not part of this path."""
+(float64 product, one rounding to float32 -- scipy's Rotation.apply).
+
+`color_jitter` (scannet_2d3d.py:241-243, T.ColorJitter on the PIL image) is applied by ops.prepare_frames to the frames picked from a
+raw uint8 store; `draw_color_jitter` / `draw_flip` below make its draws ON THE DEVICE (torchvision's law, not its draws), which is how
+scene.sample_train_batch builds a jittered, mirrored batch without a host synchronisation.  DeviceAugmentation does not touch colours."""
 import numpy as np
 import torch
 
@@ -54,3 +57,39 @@ class DeviceAugmentation(object):
             mats = np.stack([z_rotation_matrix(self.rng.uniform(low=self.z_rot[0], high=self.z_rot[1])) for _ in range(B)])
             batch['z_rot'] = torch.from_numpy(mats).to(dev)
         return batch
+
+
+def _shape(n):
+    return (int(n),) if isinstance(n, int) else tuple(int(v) for v in n)
+
+
+def draw_color_jitter(n, params, device, generator=None):
+    """The draws of torchvision's ColorJitter(brightness, contrast, saturation) for n frames (an int, or a shape such as (B, nv)), on
+    `device` without a host synchronisation.  params: the YAML's `color_jitter` 3-tuple; a fourth entry (hue) must be 0.
+    -> factor n + (3,) float32, order n + (3,) uint8 -- what ops.prepare_frames takes.  The law: every factor uniform in
+    [max(0, 1 - p), 1 + p], drawn in float64 and rounded once to float32; the order a uniform permutation of the enabled ops (the argsort
+    of three uniforms), 0 brightness, 1 contrast, 2 saturation.  A parameter of 0 disables its op: factor exactly 1, order code 3 behind
+    the enabled ones.  generator: one of `device`, or None for its global generator."""
+    p = tuple(float(v) for v in params)
+    if len(p) == 4:
+        if p[3] != 0.0:
+            raise ValueError('draw_color_jitter: hue jitter is not supported (the reference configs pass three numbers)')
+        p = p[:3]
+    if len(p) != 3 or min(p) < 0.0:
+        raise ValueError('color_jitter must be (brightness, contrast, saturation), each >= 0')
+    shape = _shape(n)
+    u = torch.rand(shape + (6,), dtype=torch.float64, generator=generator, device=device)
+    lo = [max(0.0, 1.0 - v) for v in p]
+    factor = torch.stack([u[..., i] * ((1.0 + p[i]) - lo[i]) + lo[i] if p[i] else torch.ones_like(u[..., i]) for i in range(3)], dim=-1).float()
+    keys = torch.stack([u[..., 3 + i] if p[i] else u[..., 3 + i] + 2.0 for i in range(3)], dim=-1)  # disabled ops sort behind the others
+    order = keys.argsort(dim=-1).to(torch.uint8)
+    enabled = sum(1 for v in p if v)
+    if enabled < 3:
+        order[..., enabled:] = 3
+    return factor.contiguous(), order.contiguous()
+
+
+def draw_flip(n, p, device, generator=None):
+    """n (an int or a shape) horizontal-flip flags as uint8 on `device`: 1 with probability p (`np.random.rand() < flip`,
+    scannet_2d3d.py:293), drawn on the device."""
+    return (torch.rand(_shape(n), dtype=torch.float64, generator=generator, device=device) < float(p)).to(torch.uint8)

@@ -186,13 +186,23 @@ def build_model_mvpnet_3d(cfg, net_2d=None, load_2d_ckpt=True, freeze_2d=True):
 
 def build_augmentation(cfg, rng=None):
     """DATASET.ScanNet2D3DChunks.augmentation.{flip, z_rot} of the YAML (mvpnet/data/build.py -> ScanNet2D3DChunks(flip=, z_rot=))
-    as the device-side augmentation of mvpnet_amd.augment (None when both are off).  color_jitter stays a loader transform."""
+    as the device-side augmentation of mvpnet_amd.augment (None when both are off).  color_jitter: build_color_jitter."""
     from .augment import DeviceAugmentation
     aug = cfg.DATASET.get('ScanNet2D3DChunks', {}).get('augmentation', {})
     flip, z_rot = aug.get('flip', 0.0), aug.get('z_rot', ())
     if not flip and not z_rot:
         return None
     return DeviceAugmentation(flip=flip, z_rot=z_rot, rng=rng)
+
+
+def build_color_jitter(cfg, training=True):
+    """DATASET.ScanNet2D3DChunks.augmentation.color_jitter of the YAML as the tuple scene.sample_train_batch(color_jitter=) and
+    augment.draw_color_jitter take; () when it is off, and for validation / test (mvpnet/data/build.py:116-117 passes the augmentation
+    to the training split only)."""
+    if not training:
+        return ()
+    jitter = cfg.DATASET.get('ScanNet2D3DChunks', {}).get('augmentation', {}).get('color_jitter', ())
+    return tuple(float(v) for v in jitter) if jitter else ()
 
 
 def build_optimizer(cfg, model):

@@ -158,12 +158,14 @@ def chunk_base_masks(chunk_indices, base_point_ind, n_pts):
 
 def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                   min_nb_pts=2048, overlap=None, batch_size=8, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None,
-                  pad_generator=None):
+                  pad_generator=None, image_normalizer=None, channels_last=False):
     """From a scene's raw arrays to what `infer_scene` takes: `ScanNet2D3DChunksTest.__getitem__` (mvpnet/data/scannet_2d3d.py:506-565)
     followed by `get_rgbd_data`'s frame choice (:191-221) and the sparse-chunk rule of test_mvpnet_3d.py:146-154, on the device.
 
     points (n,3) float32; depth (F,h,w) float32 m / (u)int16 mm with intrinsics cam_matrix ((3,3) or (4,4), of depth's resolution);
-    pose (F,4,4) float32; images (F,3,H,W) what the 2D network reads.  The overlap is computed from `depth` as given (the reference
+    pose (F,4,4) float32; images (F,3,H,W) what the 2D network reads, or the raw (F,H,W,3) uint8 frames: the picked ones then go through
+    ops.prepare_frames (`/ 255.` and `image_normalizer` = the YAML's (mean, std), scannet_2d3d.py:245-251; channels_last: the layout a
+    channels-last 2D network reads; no jitter at test time).  The overlap is computed from `depth` as given (the reference
     uses 80x60 maps: chunks.compute_rgbd_overlap); the batches carry the lifting-resolution maps: `lift_depth` (F,H,W), or `depth`
     itself when it already has the images' resolution, with the intrinsics' first two rows scaled by W/w and H/h (:206-210).
     overlap=(base_point_ind, overlaps) -- the reference's per-scene arrays -- skips the overlap computation.
@@ -190,7 +192,7 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
     picked = ops.select_frames_batched(overlaps if overlaps.dtype == torch.int32 else overlaps.bool(),
                                        chunk_base_masks(chunk_inds, base_point_ind, n_pts), num_rgbd_frames)  # (C,nv)
 
-    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene')
+    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene', image_normalizer, channels_last)
     box = torch.stack(boxes)[:, [0, 1, 3, 4]]  # (C,4) float64 x1,y1,x2,y2
     pixel_box = (box + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=box.device)).float().to(dev)
 
@@ -205,25 +207,34 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
     return chunk_batches, chunk_inds, n_pts
 
 
-def _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, who):
+def _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, who, image_normalizer=None, channels_last=False):
     """What every batch of a scene gathers its frames from: the lifting-resolution depth maps and the intrinsics scaled to them with
     their inverse (scannet_2d3d.py:206-210, :38), per frame, on the device."""
     import numpy as np
     ldepth = depth if lift_depth is None else lift_depth
     F, H, W = ldepth.shape
-    if images.shape[0] != F or tuple(images.shape[-2:]) != (H, W):
-        raise RuntimeError(who + ': images (F,3,H,W) and the lifting depth (F,H,W) disagree: pass lift_depth at the images\' resolution')
+    raw = images.dtype == torch.uint8
+    if images.shape[0] != F or tuple(images.shape[1:3] if raw else images.shape[-2:]) != (H, W):
+        raise RuntimeError(who + ': images (F,3,H,W) / (F,H,W,3) uint8 and the lifting depth (F,H,W) disagree: pass lift_depth at the images\' resolution')
+    if not raw and (image_normalizer is not None or channels_last):
+        raise RuntimeError(who + ': image_normalizer / channels_last apply to raw (F,H,W,3) uint8 frames only; float images are final')
     cam = (cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)).astype(np.float32)[..., :3, :3].copy()
     cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
     cam[..., 1, :] /= np.float32(depth.size(1) / H)
     kinv = np.linalg.inv(cam)  # float32, :38
     return {'images': images, 'depth': ldepth, 'pose': pose, 'cam_matrix': torch.from_numpy(cam).to(dev).expand(F, 3, 3),
-            'kinv': torch.from_numpy(np.ascontiguousarray(kinv)).to(dev).expand(F, 3, 3)}
+            'kinv': torch.from_numpy(np.ascontiguousarray(kinv)).to(dev).expand(F, 3, 3), 'image_normalizer': image_normalizer,
+            'channels_last': channels_last}
 
 
 def _chunk_batch(fr, sel, points, pixel_box, k):
     """One batch: the frames `sel` (B,nv) of `_frame_tensors`' dict beside the chunks' points (B,3,N) and pixel boxes (B,4)."""
-    return {'images': fr['images'][sel].contiguous(), 'points': points, 'depth': fr['depth'][sel].contiguous(),
+    if fr['images'].dtype == torch.uint8:
+        from . import ops
+        images = ops.prepare_frames(fr['images'], sel.contiguous(), normalizer=fr['image_normalizer'], channels_last=fr['channels_last'])
+    else:
+        images = fr['images'][sel].contiguous()
+    return {'images': images, 'points': points, 'depth': fr['depth'][sel].contiguous(),
             'cam_matrix': fr['cam_matrix'][sel].contiguous(), 'kinv': fr['kinv'][sel].contiguous(), 'pose': fr['pose'][sel].contiguous(),
             'pixel_box': pixel_box.contiguous(), 'k': int(k)}
 
@@ -263,10 +274,11 @@ def plan_buckets(lengths, min_nb_pts=2048, batch_size=32, max_batch_points=32 * 
 
 def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                            min_nb_pts=2048, overlap=None, batch_size=32, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None,
-                           pad_seed=0, max_batch_points=32 * 8192, max_bucket=32768):
+                           pad_seed=0, max_batch_points=32 * 8192, max_bucket=32768, image_normalizer=None, channels_last=False):
     """prepare_scene for a scene whose chunks have DIFFERENT sizes (the reference's test loop feeds every chunk with all its points):
     chunks of similar size share a batch after being padded to a common size (plan_buckets), with no per-chunk work on the host.
-    Arguments as prepare_scene, `pad_seed` (an int) in place of `pad_generator`; single process.
+    Arguments as prepare_scene (raw uint8 frames with `image_normalizer` / `channels_last` included), `pad_seed` (an int) in place of
+    `pad_generator`; single process.
 
     Padding is exact in eval mode: the duplicates are appended BEHIND a chunk's own points, so farthest point sampling picks the same
     indices (lowest index on ties), every ball holds the same distinct points, and the padded columns' logits are dropped by the vote.
@@ -302,7 +314,7 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
             out_base[c], out_len[c], at = at, N, at + 3 * N
     packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len, seed=pad_seed)
     picked = ops.select_frames_batched(ov, csr['base_bits'], num_rgbd_frames)  # (C,nv), the chunker's order
-    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed')
+    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed', image_normalizer, channels_last)
     pixel_box = (csr['boxes'][:, [0, 1, 3, 4]] + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=dev)).float()
     order_t = torch.tensor(order, dtype=torch.int64).to(dev)
     picked, pixel_box = picked[order_t], pixel_box[order_t]
@@ -318,28 +330,38 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
 
 
 def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2), chunk_thresh=0.3,
-                       num_tries=10, generator=None):
+                       num_tries=10, generator=None, color_jitter=(), image_normalizer=None, flip=0.0, channels_last=False):
     """One TRAINING batch from scenes resident on the device: what a batch of `ScanNet2D3DChunks.__getitem__` calls collates to
     (mvpnet/data/scannet_2d3d.py:323-398 with get_rgbd_data's frame choice, :199-221), without a host synchronisation.
     store: dict of device tensors --
         points (Ntot,3) float32, seg_label (Ntot,) int64 (mapped, negative = unlabelled), scene_offsets (S+1,) int64: the scenes, one
         after the other; base_point_ind (S,nbp) int64 inside each scene; overlap_bits (Ftot,W) int32 bit rows (ops.rgbd_overlap(...,
-        packed=True) per scene, concatenated) and frame_offsets (S+1,) int64; depth (Ftot,H,W), images (Ftot,3,H,W), pose (Ftot,4,4) at
+        packed=True) per scene, concatenated) and frame_offsets (S+1,) int64; depth (Ftot,H,W), images (Ftot,3,H,W) [or raw, below], pose (Ftot,4,4) at
         the lifting resolution; cam / kinv (S,3,3) float32: every scene's intrinsics of that resolution and their inverse.
     scene_of_chunk (B,) int64 on the device: the dataset indices of the batch.
     chunks.sample_train_chunks draws the chunks (one call), ops.select_frames_batched with the scenes' frame ranges picks the frames
     (one launch), the rest are gathers.  -> the dict MVPNet3D._forward and SegLoss read: images (B,nv,3,H,W), points (B,3,nb_pts),
     seg_label (B,nb_pts), depth (B,nv,H,W), cam_matrix / kinv (B,nv,3,3), pose (B,nv,4,4), pixel_box (B,4) = chunk_box -/+ fl32(0.1) in
-    float32 (:274-281), k.  augment.DeviceAugmentation applies to it as to any batch."""
+    float32 (:274-281), k.  augment.DeviceAugmentation applies to it as to any batch.
+
+    A RAW store -- images (Ftot,H,W,3) uint8, as the PNGs decode: a quarter of the float store's bytes -- gets the loader's image recipe
+    on the device as well (:241-252, :293-296; ops.prepare_frames on the picked frames): color_jitter = the YAML's (brightness, contrast,
+    saturation), drawn per frame by augment.draw_color_jitter; image_normalizer = the YAML's (mean, std); flip = the probability of
+    mirroring a view, drawn by augment.draw_flip -- the batch then carries 'flip' (B,nv) uint8, which MVPNet3D / ops.lift consume, so
+    DeviceAugmentation is left with z_rot only; channels_last: images with (B,nv,H,W,3) memory.  All draws come from `generator`, behind
+    the chunks' draws, in this order: jitter, flip.  A float store is final: it takes none of the four."""
     from . import chunks as CH
     ch = CH.sample_train_chunks(store['points'], store['seg_label'], store['scene_offsets'], scene_of_chunk, nb_pts, chunk_size=chunk_size,
                                 chunk_margin=chunk_margin, chunk_thresh=chunk_thresh, num_tries=num_tries,
                                 base_point_ind=store['base_point_ind'], generator=generator)
-    return assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k)
+    return assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k, color_jitter=color_jitter, image_normalizer=image_normalizer, flip=flip,
+                                channels_last=channels_last, generator=generator)
 
 
-def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k):
-    """sample_train_batch behind the draw: `ch` is ops.sample_chunks' result for the store's scenes (with base_bits)."""
+def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k, *, color_jitter=(), image_normalizer=None, flip=0.0, channels_last=False,
+                         generator=None):
+    """sample_train_batch behind the draw: `ch` is ops.sample_chunks' result for the store's scenes (with base_bits); the keyword
+    arguments are sample_train_batch's, for a raw uint8 store."""
     from . import ops
     nv = int(num_rgbd_frames)
     fo = store['frame_offsets']
@@ -348,7 +370,20 @@ def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k):
     picked = ops.select_frames_batched(store['overlap_bits'], ch['base_bits'], nv, frame_begin=begin, frame_count=count)  # (B,nv) global rows
     B = scene_of_chunk.numel()
     box = ch['chunk_box']
-    return {'images': store['images'][picked].contiguous(), 'points': ch['points'], 'seg_label': ch['seg_label'],
+    extra = {}
+    if store['images'].dtype == torch.uint8:
+        from . import augment as A
+        factor, order = A.draw_color_jitter(tuple(picked.shape), color_jitter, picked.device, generator=generator) if color_jitter else (None, None)
+        if flip:
+            extra['flip'] = A.draw_flip(tuple(picked.shape), flip, picked.device, generator=generator)
+        images = ops.prepare_frames(store['images'], picked, factor=factor, order=order, flip=extra.get('flip'), normalizer=image_normalizer,
+                                    channels_last=channels_last)
+    elif color_jitter or image_normalizer is not None or flip or channels_last:
+        raise RuntimeError('assemble_train_batch: color_jitter / image_normalizer / flip / channels_last need a raw store, images (Ftot,H,W,3) '
+                           'uint8; float images are final')
+    else:
+        images = store['images'][picked].contiguous()
+    return {'images': images, 'points': ch['points'], 'seg_label': ch['seg_label'], **extra,
             'depth': store['depth'][picked].contiguous(),
             'cam_matrix': store['cam'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
             'kinv': store['kinv'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
