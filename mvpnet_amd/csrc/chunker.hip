@@ -9,11 +9,11 @@
 //                         the list is running base + (members in the sub-tiles and waves before its own) + (members among the lower
 //                         lanes of its wave's ballot): ascending point index by construction, no atomics, no scan across workgroups
 //                         (the pattern of sample.hip's select_kernel<0> and of ball_query.hip).  The z extent rides along; the
-//                         base-point bits are written as sample.hip's finish_kernel writes them.
-//   chunks_pack_kernel  : slot s of chunk c -> a member (the pad rule of mvp_sample_chunks_f32) -> three coordinates.
+//                         base-point bits are chunk_common.h's write_base_bits.
+//   chunks_pack_kernel  : slot s of chunk c -> a member (chunk_common.h's pad rule) -> three coordinates.
 // Every window re-reads the scene (12 bytes x n, out of L2 after the first): a per-point scatter into its windows would read less but
 // needs a stable multi-split.
-#include "dropout.h"  // lowbias32
+#include "chunk_common.h"
 #include <math.h>
 
 namespace {
@@ -50,10 +50,6 @@ __device__ __forceinline__ bool outer_test(const Window& b, float x, float y) {
   const double xd = x, yd = y;
   return xd >= b.out_lx && xd <= b.out_hx && yd >= b.out_ly && yd <= b.out_hy;
 }
-
-// NaN-propagating min / max (torch.amin / amax over the members' z)
-__device__ __forceinline__ float zmin_of(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float zmax_of(float a, float b) { return (a > b || a != a) ? a : b; }
 
 __global__ __launch_bounds__(kChkThreads) void chunks_count_kernel(const float* __restrict__ points, int n,
                                                                    const float* __restrict__ corners, double sx, double sy, double mx,
@@ -120,13 +116,10 @@ __global__ __launch_bounds__(kChkThreads) void chunks_fill_kernel(FillArgs a) {
   __shared__ int s_tot[2][kUnroll][kChkWaves];
   __shared__ float s_z[kChkWaves][2];
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int w = a.kept[c];
-  w = w < 0 ? 0 : (w >= a.nc ? a.nc - 1 : w);
-  const Window b = window_of(a.corners, w, a.sx, a.sy, a.mx, a.my);
+  const Window b = window_of(a.corners, (int)clamp_index(a.kept[c], a.nc), a.sx, a.sy, a.mx, a.my);
   // the chunk's slice of `index`, cut to the array: a list longer than its slice loses its tail, nothing is written outside
   int64_t off = a.offsets[c], end = a.offsets[c + 1];
-  off = off < 0 ? 0 : (off > a.total ? a.total : off);
-  end = end < off ? off : (end > a.total ? a.total : end);
+  clamp_slice(off, end, a.total);
   const int64_t cap = end - off;
   const unsigned long long below = (1ull << lane) - 1ull;
   int64_t run = 0;
@@ -154,8 +147,8 @@ __global__ __launch_bounds__(kChkThreads) void chunks_fill_kernel(FillArgs a) {
       before[u] = __popcll(bal & below);
       if (lane == 0) s_tot[par][u][wave] = __popcll(bal);
       if (in[u]) {
-        zlo = zmin_of(zlo, z[u]);
-        zhi = zmax_of(zhi, z[u]);
+        zlo = nan_min(zlo, z[u]);
+        zhi = nan_max(zhi, z[u]);
       }
     }
     __syncthreads();  // one barrier per tile: the next tile writes the other half of s_tot
@@ -176,8 +169,8 @@ __global__ __launch_bounds__(kChkThreads) void chunks_fill_kernel(FillArgs a) {
   }
 #pragma unroll
   for (int k = kWave / 2; k >= 1; k >>= 1) {
-    zlo = zmin_of(zlo, __shfl_xor(zlo, k, kWave));
-    zhi = zmax_of(zhi, __shfl_xor(zhi, k, kWave));
+    zlo = nan_min(zlo, __shfl_xor(zlo, k, kWave));
+    zhi = nan_max(zhi, __shfl_xor(zhi, k, kWave));
   }
   if (lane == 0) {
     s_z[wave][0] = zlo;
@@ -187,27 +180,17 @@ __global__ __launch_bounds__(kChkThreads) void chunks_fill_kernel(FillArgs a) {
   if (tid == 0) {
 #pragma unroll
     for (int v = 1; v < kChkWaves; ++v) {
-      zlo = zmin_of(zlo, s_z[v][0]);
-      zhi = zmax_of(zhi, s_z[v][1]);
+      zlo = nan_min(zlo, s_z[v][0]);
+      zhi = nan_max(zhi, s_z[v][1]);
     }
     a.zbox[(size_t)c * 2 + 0] = zlo;
     a.zbox[(size_t)c * 2 + 1] = zhi;
   }
-  if (a.nb > 0) {  // bit j: base point j is a member; 64 base points per wave and step, two words per ballot
-    const int W = (a.nb + 31) >> 5;
-    for (int j0 = wave * kWave; j0 < a.nb; j0 += kChkThreads) {
-      const int j = j0 + lane;
-      bool in = false;
-      if (j < a.nb) {
-        int64_t p = a.base_point_ind[j];
-        p = p < 0 ? 0 : (p >= a.n ? a.n - 1 : p);
-        in = outer_test(b, a.points[p * 3 + 0], a.points[p * 3 + 1]);
-      }
-      const unsigned long long bal = __ballot(in);
-      const int word = (j0 >> 5) + (lane >> 5);
-      if ((lane & 31) == 0 && word < W) a.base_bits[(size_t)c * W + word] = (uint32_t)(bal >> (lane & 32));
-    }
-  }
+  if (a.nb > 0)  // bit j: base point j is a member
+    write_base_bits<kChkThreads>(a.base_bits + (size_t)c * ((a.nb + 31) >> 5), a.nb, [&](int j) {
+      const int64_t p = clamp_index(a.base_point_ind[j], a.n);
+      return outer_test(b, a.points[p * 3 + 0], a.points[p * 3 + 1]);
+    });
 }
 
 __global__ __launch_bounds__(kChkThreads) void chunks_pack_kernel(const float* __restrict__ points, int64_t n,
@@ -218,16 +201,13 @@ __global__ __launch_bounds__(kChkThreads) void chunks_pack_kernel(const float* _
                                                                   float* __restrict__ out) {
   const int c = blockIdx.y;
   int64_t off = offsets[c], end = offsets[c + 1];
-  off = off < 0 ? 0 : (off > total ? total : off);
-  end = end < off ? off : (end > total ? total : end);
+  clamp_slice(off, end, total);
   const int64_t nc = end - off, N = out_len[c], ob = out_base[c];
   // the chunk's (3, N) rows lie inside `out`, or nothing of it is written
   if (N <= 0 || nc <= 0 || nc >= (1ll << 32) || ob < 0 || ob > out_floats || 3 * N > out_floats - ob) return;
-  const uint32_t sc = lowbias32(seed32 + 0x9E3779B9u * (uint32_t)(c + 1));
+  const uint32_t sc = chunk_seed(seed32, c);
   for (int64_t s = (int64_t)blockIdx.x * kChkThreads + threadIdx.x; s < N; s += (int64_t)gridDim.x * kChkThreads) {
-    const int64_t m = s < nc ? s : (int64_t)(((unsigned long long)lowbias32((uint32_t)s ^ sc ^ 0x85EBCA6Bu) * (unsigned long long)nc) >> 32);
-    int64_t p = index[off + m];
-    p = p < 0 ? 0 : (p >= n ? n - 1 : p);
+    const int64_t p = clamp_index(index[off + pad_member(s, nc, sc)], n);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[ob + k * N + s] = points[p * 3 + k];
   }

@@ -17,7 +17,7 @@
 //   finish_kernel  : one workgroup per chunk: bitonic sort of the pairs in LDS (crop) or the pad rule, then the gather of points and
 //                    labels and the base-point bits.
 // Measurements: DESIGN.md (training chunks).
-#include "dropout.h"  // lowbias32
+#include "chunk_common.h"
 #include <math.h>
 
 namespace {
@@ -53,11 +53,9 @@ struct Scene {
 // scene of chunk b; indices and offsets are clamped into the arrays, so wrong arguments give wrong results and never a stray access
 __device__ __forceinline__ Scene scene_of(const int64_t* __restrict__ scene_offsets, const int64_t* __restrict__ scene_of_chunk, int b,
                                           int S, int64_t Ntot, int G) {
-  int64_t s = scene_of_chunk[b];
-  s = s < 0 ? 0 : (s >= S ? S - 1 : s);
+  const int64_t s = clamp_index(scene_of_chunk[b], S);
   int64_t off = scene_offsets[s], end = scene_offsets[s + 1];
-  off = off < 0 ? 0 : (off > Ntot ? Ntot : off);
-  end = end < off ? off : (end > Ntot ? Ntot : end);
+  clamp_slice(off, end, Ntot);
   Scene sc;
   sc.off = off;
   sc.n = (int32_t)(end - off);
@@ -65,10 +63,6 @@ __device__ __forceinline__ Scene scene_of(const int64_t* __restrict__ scene_offs
   sc.seg = (per + kSmpThreads - 1) / kSmpThreads * kSmpThreads;
   return sc;
 }
-
-// NaN-propagating min / max (numpy.min / numpy.max, :365-366)
-__device__ __forceinline__ float pmin(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float pmax(float a, float b) { return (a > b || a != a) ? a : b; }
 
 // the box of a try in BT = float (ScanNet2D3DChunks) or double (ScanNet3DChunks): (c -/+ half) -/+ margin, each operation rounded once
 template <typename BT>
@@ -78,7 +72,7 @@ __device__ __forceinline__ void try_box(const float* __restrict__ points, const 
     lox = loy = hix = hiy = (BT)NAN;
     return;
   }
-  ci = ci < 0 ? 0 : (ci >= sc.n ? sc.n - 1 : ci);
+  ci = clamp_index(ci, sc.n);
   const BT cx = (BT)points[(sc.off + ci) * 3 + 0], cy = (BT)points[(sc.off + ci) * 3 + 1];
   lox = (cx - hx) - mx;
   loy = (cy - hy) - my;
@@ -112,10 +106,10 @@ __global__ __launch_bounds__(kSmpThreads) void count_kernel(const float* __restr
       xf = points[(sc.off + j) * 3 + 0];
       yf = points[(sc.off + j) * 3 + 1];
       lab = label[sc.off + j] >= 0;
-      mnx = pmin(mnx, xf);
-      mny = pmin(mny, yf);
-      mxx = pmax(mxx, xf);
-      mxy = pmax(mxy, yf);
+      mnx = nan_min(mnx, xf);
+      mny = nan_min(mny, yf);
+      mxx = nan_max(mxx, xf);
+      mxy = nan_max(mxy, yf);
     }
     const BT x = (BT)xf, y = (BT)yf;
     for (int t = 0; t < T; ++t) {
@@ -129,10 +123,10 @@ __global__ __launch_bounds__(kSmpThreads) void count_kernel(const float* __restr
   }
 #pragma unroll
   for (int k = kWave / 2; k >= 1; k >>= 1) {
-    mnx = pmin(mnx, __shfl_xor(mnx, k, kWave));
-    mny = pmin(mny, __shfl_xor(mny, k, kWave));
-    mxx = pmax(mxx, __shfl_xor(mxx, k, kWave));
-    mxy = pmax(mxy, __shfl_xor(mxy, k, kWave));
+    mnx = nan_min(mnx, __shfl_xor(mnx, k, kWave));
+    mny = nan_min(mny, __shfl_xor(mny, k, kWave));
+    mxx = nan_max(mxx, __shfl_xor(mxx, k, kWave));
+    mxy = nan_max(mxy, __shfl_xor(mxy, k, kWave));
   }
   if (lane < T) {
     s_m[wave][lane] = mc;
@@ -158,10 +152,10 @@ __global__ __launch_bounds__(kSmpThreads) void count_kernel(const float* __restr
     float4 e = make_float4(s_ext[0][0], s_ext[0][1], s_ext[0][2], s_ext[0][3]);
 #pragma unroll
     for (int w = 1; w < kSmpThreads / kWave; ++w) {
-      e.x = pmin(e.x, s_ext[w][0]);
-      e.y = pmin(e.y, s_ext[w][1]);
-      e.z = pmax(e.z, s_ext[w][2]);
-      e.w = pmax(e.w, s_ext[w][3]);
+      e.x = nan_min(e.x, s_ext[w][0]);
+      e.y = nan_min(e.y, s_ext[w][1]);
+      e.z = nan_max(e.z, s_ext[w][2]);
+      e.w = nan_max(e.w, s_ext[w][3]);
     }
     pbox[(size_t)b * G + g] = e;
   }
@@ -221,10 +215,10 @@ __global__ __launch_bounds__(kSmpThreads) void pick_kernel(PickArgs a) {
     float4 e = lane < G ? a.pbox[(size_t)b * G + lane] : make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY);
 #pragma unroll
     for (int k = kWave / 2; k >= 1; k >>= 1) {
-      e.x = pmin(e.x, __shfl_xor(e.x, k, kWave));
-      e.y = pmin(e.y, __shfl_xor(e.y, k, kWave));
-      e.z = pmax(e.z, __shfl_xor(e.z, k, kWave));
-      e.w = pmax(e.w, __shfl_xor(e.w, k, kWave));
+      e.x = nan_min(e.x, __shfl_xor(e.x, k, kWave));
+      e.y = nan_min(e.y, __shfl_xor(e.y, k, kWave));
+      e.z = nan_max(e.z, __shfl_xor(e.z, k, kWave));
+      e.w = nan_max(e.w, __shfl_xor(e.w, k, kWave));
     }
     lox = e.x - (float)a.mx, loy = e.y - (float)a.my, hix = e.z + (float)a.mx, hiy = e.w + (float)a.my;
     mw = sc.n;
@@ -257,7 +251,7 @@ __global__ __launch_bounds__(kSmpThreads) void pick_kernel(PickArgs a) {
     st.m = mw;
     st.all = win < 0;
     st.crop = mw >= a.nb_pts;
-    st.sb = lowbias32(seed32 + 0x9E3779B9u * (uint32_t)(b + 1));
+    st.sb = chunk_seed(seed32, b);
     st.prefix = 0u;
     st.rank = a.nb_pts;
     st.taken = 0;
@@ -417,7 +411,7 @@ struct FinishArgs {
 __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinishArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sample_smem[];
   unsigned long long* buf = reinterpret_cast<unsigned long long*>(sample_smem);  // P pairs, P = nb_pts rounded up to a power of two
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int b = blockIdx.x, tid = threadIdx.x;
   const ChunkState st = a.state[b];
   const int nb = a.nb_pts, P = a.P;
   if (st.crop) {
@@ -445,10 +439,9 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinishArgs a) {
     } else if (st.m <= 0) {
       idx = 0;
     } else {
-      const int slot = s < st.m ? s : (int)(((unsigned long long)lowbias32((uint32_t)s ^ st.sb ^ 0x85EBCA6Bu) * (unsigned)st.m) >> 32);
-      idx = a.members[(size_t)b * nb + slot];
+      idx = a.members[(size_t)b * nb + pad_member(s, st.m, st.sb)];
     }
-    idx = idx < 0 ? 0 : (idx >= st.n ? st.n - 1 : idx);
+    idx = clamp_index(idx, st.n);  // (-1 for a scene without points)
     a.choice[(size_t)b * nb + s] = idx < 0 ? 0 : idx;
     const bool ok = st.n > 0;
     const size_t p = (size_t)(st.off + idx);
@@ -456,22 +449,13 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinishArgs a) {
     for (int c = 0; c < 3; ++c) a.out_points[((size_t)b * 3 + c) * nb + s] = ok ? a.points[p * 3 + c] : 0.f;
     a.out_label[(size_t)b * nb + s] = ok ? a.label[p] : -100;
   }
-  if (a.nbp > 0) {  // bit j: base point j of the chunk's scene is a member (:200-204); 64 base points per wave and step
-    int64_t sidx = a.scene_of_chunk[b];
-    sidx = sidx < 0 ? 0 : (sidx >= a.S ? a.S - 1 : sidx);
-    const int W = (a.nbp + 31) >> 5;
-    for (int j0 = (tid / kWave) * kWave; j0 < a.nbp; j0 += kFinThreads) {
-      const int j = j0 + lane;
-      bool in = false;
-      if (j < a.nbp && st.n > 0) {
-        int64_t p = a.base_point_ind[(size_t)sidx * a.nbp + j];
-        p = p < 0 ? 0 : (p >= st.n ? st.n - 1 : p);
-        in = is_member(st, a.points[(st.off + p) * 3 + 0], a.points[(st.off + p) * 3 + 1]);
-      }
-      const unsigned long long bal = __ballot(in);
-      const int w = (j0 >> 5) + (lane >> 5);
-      if ((lane & 31) == 0 && w < W) a.base_bits[(size_t)b * W + w] = (uint32_t)(bal >> (lane & 32));
-    }
+  if (a.nbp > 0) {  // bit j: base point j of the chunk's scene is a member (:200-204)
+    const int64_t sidx = clamp_index(a.scene_of_chunk[b], a.S);
+    write_base_bits<kFinThreads>(a.base_bits + (size_t)b * ((a.nbp + 31) >> 5), a.nbp, [&](int j) {
+      if (st.n <= 0) return false;
+      const int64_t p = clamp_index(a.base_point_ind[(size_t)sidx * a.nbp + j], st.n);
+      return is_member(st, a.points[(st.off + p) * 3 + 0], a.points[(st.off + p) * 3 + 1]);
+    });
   }
 }
 

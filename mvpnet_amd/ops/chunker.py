@@ -4,9 +4,9 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .overlap import MAX_BASE_POINTS  # MVP_OVERLAP_MAX_BASE
 
-MAX_WINDOWS = 65535     # MVP_CHUNKER_MAX_WINDOWS
-MAX_BASE_POINTS = 4096  # MVP_OVERLAP_MAX_BASE
+MAX_WINDOWS = 65535  # MVP_CHUNKER_MAX_WINDOWS
 
 
 def supported(n, nc, nb=0):

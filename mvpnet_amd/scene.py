@@ -6,7 +6,9 @@ r, r+W, ... (dist.shard_chunks), runs them in batches with the coordinate-only w
 stream, the per-chunk logits are all-gathered ONCE (RCCL over xGMI) and every rank votes on the device (dist.vote_scene)."""
 import torch
 
+from . import chunks as CH
 from . import dist as D
+from . import ops
 from .mvpnet3d import prefetch_geometry
 
 
@@ -18,8 +20,7 @@ def pad_sparse_chunk(data, min_nb_pts=2048, generator=None):
     n = data['points'].size(1)
     if n >= min_nb_pts:
         return data
-    pad = torch.randint(n, (min_nb_pts - n,), generator=generator, device='cpu').to(data['points'].device)
-    choice = torch.cat([torch.arange(n, device=pad.device), pad])
+    choice = CH.crop_pad_choice(n, min_nb_pts, generator=generator, device='cpu').to(data['points'].device)  # drawn on the host
     out = dict(data, points=data['points'][:, choice])
     if 'knn_indices' in data:
         out['knn_indices'] = data['knn_indices'][choice]
@@ -144,18 +145,6 @@ def infer_scene_votes(model, points, feature=None, nb_pts=32768, num_votes=3, vo
     return mean, label, vote_inds
 
 
-def chunk_base_masks(chunk_indices, base_point_ind, n_pts):
-    """bool (C, nb): base point j lies in chunk c (`base_point_mask[base_point_ind]` of scannet_2d3d.py:199-204, for all chunks).
-    Goes through a (C, n_pts) bool membership matrix: 12.8 MB for 64 chunks of a 200 000-point scene, C * n_pts bytes in general."""
-    dev = base_point_ind.device
-    C = len(chunk_indices)
-    member = torch.zeros((C, n_pts), dtype=torch.bool, device=dev)
-    if C:
-        rows = torch.repeat_interleave(torch.arange(C, device=dev), torch.tensor([int(c.numel()) for c in chunk_indices], device=dev))
-        member[rows, torch.cat(chunk_indices)] = True
-    return member[:, base_point_ind]
-
-
 def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                   min_nb_pts=2048, overlap=None, batch_size=8, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None,
                   pad_generator=None, image_normalizer=None, channels_last=False):
@@ -173,70 +162,95 @@ def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_
     The result lists ALL chunks of the scene, i.e. what a single process hands to infer_scene; with several ranks every rank passes
     infer_scene the batches of its own shard (dist.shard_chunks) and the full chunk_inds.  Beyond the reference's arguments:
     `lift_depth`, `num_base_pts` / `radius` / `generator` (handed to chunks.compute_rgbd_overlap) and `pad_generator` (pad_sparse_chunk).
-    All chunks' frames are chosen by ONE ops.select_frames_batched call.  Every chunk is fed whole (nb_pts = -1), padded to
-    `min_nb_pts` by pad_sparse_chunk; consecutive chunks of equal size share a batch of up to `batch_size`, the chunk order is kept.
+    The chunks and their base-point bit rows come from chunks.scene2chunks_csr (the chunker kernels; no membership matrices), all chunks'
+    frames from ONE ops.select_frames_batched call on bit rows.  The base points are needed before the chunker runs: for a scene in which
+    no window is kept, `generator` has been drawn from and `num_base_pts > n` raises before ([], [], n_pts) is returned.  Every chunk is fed
+    whole (nb_pts = -1), padded to `min_nb_pts` by pad_sparse_chunk; consecutive chunks of equal size share a batch of up to `batch_size`,
+    the chunk order is kept.
     -> (chunk_batches, chunk_inds, n_pts) with the keys MVPNet3D._forward reads: images (B,nv,3,H,W), points (B,3,N), depth (B,nv,H,W),
     cam_matrix / kinv (B,nv,3,3), pose (B,nv,4,4), pixel_box (B,4) = chunk box -/+ 0.1 m (:274-281), k."""
-    from . import chunks as CH
-    from . import ops
-    dev = points.device
-    n_pts = points.size(0)
-    chunk_inds, boxes = CH.scene2chunks_legacy(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin, return_bbox=True)
-    if not chunk_inds:
+    csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
+                        num_base_pts, radius, generator)
+    lengths, n_pts = csr['lengths'], points.size(0)
+    if not lengths:
         return [], [], n_pts
-    if overlap is None:
-        overlap = CH.compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=num_base_pts, radius=radius, generator=generator)
-    base_point_ind, overlaps = overlap
-    base_point_ind = torch.as_tensor(base_point_ind).to(dev).long()
-    overlaps = torch.as_tensor(overlaps).to(dev)
-    picked = ops.select_frames_batched(overlaps if overlaps.dtype == torch.int32 else overlaps.bool(),
-                                       chunk_base_masks(chunk_inds, base_point_ind, n_pts), num_rgbd_frames)  # (C,nv)
-
-    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene', image_normalizer, channels_last)
-    box = torch.stack(boxes)[:, [0, 1, 3, 4]]  # (C,4) float64 x1,y1,x2,y2
-    pixel_box = (box + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=box.device)).float().to(dev)
-
+    batch = _scene_batcher(points.device, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene', k, image_normalizer, channels_last)
+    chunk_inds = list(torch.split(csr['index'], lengths))
     singles = [pad_sparse_chunk({'points': points[ind].t().contiguous()}, min_nb_pts=min_nb_pts, generator=pad_generator)['points'] for ind in chunk_inds]
     chunk_batches, lo = [], 0
     while lo < len(singles):
         hi = lo + 1
         while hi < len(singles) and hi - lo < batch_size and singles[hi].size(1) == singles[lo].size(1):
             hi += 1
-        chunk_batches.append(_chunk_batch(fr, picked[lo:hi], torch.stack(singles[lo:hi]).contiguous(), pixel_box[lo:hi], k))
+        chunk_batches.append(batch(csr['picked'][lo:hi], torch.stack(singles[lo:hi]).contiguous(), csr['pixel_box'][lo:hi]))
         lo = hi
     return chunk_batches, chunk_inds, n_pts
 
 
-def _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, who, image_normalizer=None, channels_last=False):
-    """What every batch of a scene gathers its frames from: the lifting-resolution depth maps and the intrinsics scaled to them with
-    their inverse (scannet_2d3d.py:206-210, :38), per frame, on the device."""
+def _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_base_pts,
+                  radius, generator):
+    """What prepare_scene and prepare_scene_bucketed share: the scene's chunks and their frames, in the chunker's order.
+    -> chunks.scene2chunks_csr's dict (called with the overlap's base points) + picked (C,nv) int64: ONE ops.select_frames_batched call on
+    bit rows -- the overlap's (given, or chunks.compute_rgbd_overlap's) and the chunker's base_bits -- and pixel_box (C,4) float32."""
+    dev = points.device
+    if overlap is None:
+        base_point_ind, ov = CH.compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=num_base_pts, radius=radius, generator=generator,
+                                                     packed=True)
+    else:
+        base_point_ind, ov = overlap
+        base_point_ind = torch.as_tensor(base_point_ind).to(dev).long()
+        ov = torch.as_tensor(ov).to(dev)
+        ov = ov if ov.dtype == torch.int32 else ops.pack_bits(ov.bool().t())
+    csr = CH.scene2chunks_csr(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin, base_point_ind=base_point_ind.contiguous())
+    if csr['lengths']:
+        csr['picked'] = ops.select_frames_batched(ov, csr['base_bits'], num_rgbd_frames)
+        csr['pixel_box'] = (csr['boxes'][:, [0, 1, 3, 4]] + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=dev)).float()
+    return csr
+
+
+def _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, who, k, image_normalizer=None, channels_last=False):
+    """-> batch(sel, points, pixel_box): one batch of a scene, the frames `sel` (B,nv) beside the chunks' points (B,3,N) and pixel boxes (B,4).
+    The frames come from the lifting-resolution depth maps and the intrinsics scaled to them with their inverse (scannet_2d3d.py:206-210,
+    :38), per frame, on the device."""
     import numpy as np
     ldepth = depth if lift_depth is None else lift_depth
     F, H, W = ldepth.shape
-    raw = images.dtype == torch.uint8
+    raw = _raw_frames(who, images, image_normalizer=image_normalizer is not None, channels_last=channels_last)
     if images.shape[0] != F or tuple(images.shape[1:3] if raw else images.shape[-2:]) != (H, W):
         raise RuntimeError(who + ': images (F,3,H,W) / (F,H,W,3) uint8 and the lifting depth (F,H,W) disagree: pass lift_depth at the images\' resolution')
-    if not raw and (image_normalizer is not None or channels_last):
-        raise RuntimeError(who + ': image_normalizer / channels_last apply to raw (F,H,W,3) uint8 frames only; float images are final')
     cam = (cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)).astype(np.float32)[..., :3, :3].copy()
     cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
     cam[..., 1, :] /= np.float32(depth.size(1) / H)
-    kinv = np.linalg.inv(cam)  # float32, :38
-    return {'images': images, 'depth': ldepth, 'pose': pose, 'cam_matrix': torch.from_numpy(cam).to(dev).expand(F, 3, 3),
-            'kinv': torch.from_numpy(np.ascontiguousarray(kinv)).to(dev).expand(F, 3, 3), 'image_normalizer': image_normalizer,
-            'channels_last': channels_last}
+    kinv = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(cam))).to(dev).expand(F, 3, 3)  # float32, :38
+    cam = torch.from_numpy(cam).to(dev).expand(F, 3, 3)
+    return lambda sel, points, pixel_box: {**_picked_views(images, ldepth, pose, sel, image_normalizer, channels_last), 'points': points,
+                                           'cam_matrix': cam[sel].contiguous(), 'kinv': kinv[sel].contiguous(),
+                                           'pixel_box': pixel_box.contiguous(), 'k': int(k)}
 
 
-def _chunk_batch(fr, sel, points, pixel_box, k):
-    """One batch: the frames `sel` (B,nv) of `_frame_tensors`' dict beside the chunks' points (B,3,N) and pixel boxes (B,4)."""
-    if fr['images'].dtype == torch.uint8:
-        from . import ops
-        images = ops.prepare_frames(fr['images'], sel.contiguous(), normalizer=fr['image_normalizer'], channels_last=fr['channels_last'])
+def _raw_frames(who, images, **given):
+    """True for raw (F,H,W,3) uint8 frames.  Float images are final: `who` refuses the image options `given` as true."""
+    raw = images.dtype == torch.uint8
+    if not raw and any(given.values()):
+        raise RuntimeError('{}: {} need raw (F,H,W,3) uint8 frames; float images are final'.format(who, ' / '.join(n for n in given if given[n])))
+    return raw
+
+
+def _picked_views(images, depth, pose, sel, image_normalizer=None, channels_last=False, color_jitter=(), flip=0.0, generator=None):
+    """The views `sel` (B,nv) of a frame store as a batch carries them: images, depth, pose [, flip].  Raw (F,H,W,3) uint8 images go
+    through ops.prepare_frames with the loader's recipe -- the jitter and the flips are drawn here from `generator`, in this order --; float
+    images are final (the caller has asked _raw_frames): a plain gather."""
+    out = {'depth': depth[sel].contiguous(), 'pose': pose[sel].contiguous()}
+    if images.dtype == torch.uint8:
+        from . import augment as A
+        factor, order = A.draw_color_jitter(tuple(sel.shape), color_jitter, sel.device, generator=generator) if color_jitter else (None, None)
+        if flip:
+            out['flip'] = A.draw_flip(tuple(sel.shape), flip, sel.device, generator=generator)
+        out['images'] = ops.prepare_frames(images, sel.contiguous(), factor=factor, order=order, flip=out.get('flip'), normalizer=image_normalizer,
+                                           channels_last=channels_last)
     else:
-        images = fr['images'][sel].contiguous()
-    return {'images': images, 'points': points, 'depth': fr['depth'][sel].contiguous(),
-            'cam_matrix': fr['cam_matrix'][sel].contiguous(), 'kinv': fr['kinv'][sel].contiguous(), 'pose': fr['pose'][sel].contiguous(),
-            'pixel_box': pixel_box.contiguous(), 'k': int(k)}
+        out['images'] = images[sel].contiguous()
+    return out
 
 
 def bucket_size(n, min_nb_pts, max_bucket):
@@ -289,20 +303,9 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
     BATCHES' ORDER, so `infer_scene(model, chunk_batches, chunk_inds, n_pts)` works as it stands; order[i] = the chunker's number
     (scene2chunks_legacy's position) of the i-th chunk.  The vote adds a point's logits in this order, not in the chunker's: sums differ
     from prepare_scene's in the last bits only."""
-    from . import chunks as CH
-    from . import ops
-    dev = points.device
-    n_pts = points.size(0)
-    if overlap is None:
-        base_point_ind, ov = CH.compute_rgbd_overlap(points, depth, cam_matrix, pose, num_base_pts=num_base_pts, radius=radius, generator=generator,
-                                                     packed=True)
-    else:
-        base_point_ind, ov = overlap
-        base_point_ind = torch.as_tensor(base_point_ind).to(dev).long()
-        ov = torch.as_tensor(ov).to(dev)
-        ov = ov if ov.dtype == torch.int32 else ops.pack_bits(ov.bool().t())
-    csr = CH.scene2chunks_csr(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin, base_point_ind=base_point_ind.contiguous())
-    lengths = csr['lengths']
+    csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
+                        num_base_pts, radius, generator)
+    lengths, n_pts, dev = csr['lengths'], points.size(0), points.device
     if not lengths:
         return [], [], n_pts, []
     if min(lengths) < 1:
@@ -313,20 +316,16 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
         for c in members:
             out_base[c], out_len[c], at = at, N, at + 3 * N
     packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len, seed=pad_seed)
-    picked = ops.select_frames_batched(ov, csr['base_bits'], num_rgbd_frames)  # (C,nv), the chunker's order
-    fr = _frame_tensors(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed', image_normalizer, channels_last)
-    pixel_box = (csr['boxes'][:, [0, 1, 3, 4]] + torch.tensor([-0.1, -0.1, 0.1, 0.1], dtype=torch.float64, device=dev)).float()
+    batch = _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed', k, image_normalizer, channels_last)
     order_t = torch.tensor(order, dtype=torch.int64).to(dev)
-    picked, pixel_box = picked[order_t], pixel_box[order_t]
+    picked, pixel_box = csr['picked'][order_t], csr['pixel_box'][order_t]
     chunk_batches, lo = [], 0
     for N, members in batches:
         hi, first = lo + len(members), out_base[members[0]]
-        chunk_batches.append(_chunk_batch(fr, picked[lo:hi], packed[first:first + len(members) * 3 * N].view(len(members), 3, N), pixel_box[lo:hi], k))
+        chunk_batches.append(batch(picked[lo:hi], packed[first:first + len(members) * 3 * N].view(len(members), 3, N), pixel_box[lo:hi]))
         lo = hi
-    offs = [0]
-    for n in lengths:
-        offs.append(offs[-1] + n)
-    return chunk_batches, [csr['index'][offs[c]:offs[c + 1]] for c in order], n_pts, order
+    chunk_inds = torch.split(csr['index'], lengths)
+    return chunk_batches, [chunk_inds[c] for c in order], n_pts, order
 
 
 def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2), chunk_thresh=0.3,
@@ -350,7 +349,6 @@ def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chu
     mirroring a view, drawn by augment.draw_flip -- the batch then carries 'flip' (B,nv) uint8, which MVPNet3D / ops.lift consume, so
     DeviceAugmentation is left with z_rot only; channels_last: images with (B,nv,H,W,3) memory.  All draws come from `generator`, behind
     the chunks' draws, in this order: jitter, flip.  A float store is final: it takes none of the four."""
-    from . import chunks as CH
     ch = CH.sample_train_chunks(store['points'], store['seg_label'], store['scene_offsets'], scene_of_chunk, nb_pts, chunk_size=chunk_size,
                                 chunk_margin=chunk_margin, chunk_thresh=chunk_thresh, num_tries=num_tries,
                                 base_point_ind=store['base_point_ind'], generator=generator)
@@ -362,30 +360,16 @@ def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k, *, color
                          generator=None):
     """sample_train_batch behind the draw: `ch` is ops.sample_chunks' result for the store's scenes (with base_bits); the keyword
     arguments are sample_train_batch's, for a raw uint8 store."""
-    from . import ops
+    _raw_frames('assemble_train_batch', store['images'], color_jitter=color_jitter, image_normalizer=image_normalizer is not None, flip=flip,
+                channels_last=channels_last)
     nv = int(num_rgbd_frames)
     fo = store['frame_offsets']
     begin = fo[scene_of_chunk]
     count = fo[scene_of_chunk + 1] - begin
     picked = ops.select_frames_batched(store['overlap_bits'], ch['base_bits'], nv, frame_begin=begin, frame_count=count)  # (B,nv) global rows
-    B = scene_of_chunk.numel()
-    box = ch['chunk_box']
-    extra = {}
-    if store['images'].dtype == torch.uint8:
-        from . import augment as A
-        factor, order = A.draw_color_jitter(tuple(picked.shape), color_jitter, picked.device, generator=generator) if color_jitter else (None, None)
-        if flip:
-            extra['flip'] = A.draw_flip(tuple(picked.shape), flip, picked.device, generator=generator)
-        images = ops.prepare_frames(store['images'], picked, factor=factor, order=order, flip=extra.get('flip'), normalizer=image_normalizer,
-                                    channels_last=channels_last)
-    elif color_jitter or image_normalizer is not None or flip or channels_last:
-        raise RuntimeError('assemble_train_batch: color_jitter / image_normalizer / flip / channels_last need a raw store, images (Ftot,H,W,3) '
-                           'uint8; float images are final')
-    else:
-        images = store['images'][picked].contiguous()
-    return {'images': images, 'points': ch['points'], 'seg_label': ch['seg_label'], **extra,
-            'depth': store['depth'][picked].contiguous(),
+    B, box = scene_of_chunk.numel(), ch['chunk_box']
+    return {**_picked_views(store['images'], store['depth'], store['pose'], picked, image_normalizer, channels_last,
+                            color_jitter, flip, generator), 'points': ch['points'], 'seg_label': ch['seg_label'],
             'cam_matrix': store['cam'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
             'kinv': store['kinv'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
-            'pose': store['pose'][picked].contiguous(),
             'pixel_box': torch.cat([box[:, :2] - 0.1, box[:, 2:] + 0.1], dim=1), 'k': int(k)}

@@ -117,8 +117,8 @@ def main():
         raise SystemExit('bench_scene_prep needs the GPU: nothing here is measured on a CPU')
     import mvpnet_amd.ops as ops
     from mvpnet_amd import _lib as L
-    from mvpnet_amd.chunks import scene2chunks_legacy, select_frames
-    from mvpnet_amd.scene import prepare_scene, chunk_base_masks
+    from mvpnet_amd.chunks import scene2chunks_legacy, select_frames, chunk_base_masks
+    from mvpnet_amd.scene import prepare_scene
     from mvpnet_amd.synthetic import make_rgbd_scene
     dev = torch.device('cuda:0')
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
