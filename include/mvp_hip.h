@@ -364,6 +364,45 @@ int mvp_sample_chunks_f32(const float* points, const int64_t* seg_label, const i
                           float* out_points, int64_t* out_label, float* chunk_box, int32_t* try_index, int32_t* num_members,
                           uint32_t* base_bits, void* workspace, int64_t workspace_bytes, mvp_stream_t stream);
 
+/* ---- 3D-baseline batches (NEW on the device; the reference crops, pads and rotates in a data-loader worker) ----
+ * mvp_sample_scenes_f32: `CropPad(nb_pts)` (mvpnet/data/transforms.py:112-133) of B whole resident scenes, what ScanNet3DScene feeds
+ * (mvpnet/data/scannet_3d.py:206-221; configs/scannet/3d_baselines/pn2ssg_scene.yaml crops to 32768), without a host synchronisation
+ * and without an allocation (graph-capturable on one stream).
+ *   scene_offsets (S+1,) int64; scene_of_row (B,) int64 (a scene may occur more than once); seed / seed_device exactly as in
+ *   mvp_sample_chunks_f32.  All on the device; out-of-range scene numbers and offsets are clamped into the arrays (a wrong result,
+ *   never a stray access).
+ * The draw is mvp_sample_chunks_f32's resampling rule with EVERY point of the scene a member: h = lowbias32, seed32 = low ^ high word of
+ * the seed, s_b = h(seed32 + 0x9E3779B9 * (b+1)), n = the scene's point count;
+ *   pad (n < nb_pts):   choice[b,s] = s for s < n, ((uint64)h(s ^ s_b ^ 0x85EBCA6B) * n) >> 32 for s >= n;
+ *   crop (n >= nb_pts): point j has key h(j ^ s_b) (distinct keys), choice[b,s] = the point with the s-th smallest key.
+ *   At nb_pts <= MVP_SAMPLE_MAX_PTS this is, bit for bit, the choice of mvp_sample_chunks_f32's whole-scene fallback for the same seed.
+ * Outputs: choice (B,nb_pts) int64 indices inside the scene; num_points (B,) int32 = n.  A scene without points: choice = 0, n = 0.
+ * Every result is a function of the arguments alone (integer counts, distinct keys): bit-reproducible.
+ * Limits: nb_pts <= MVP_SAMPLE_SCENE_MAX_PTS (what the sampler's multi-workgroup FPS serves), Ntot < 2^31, B <= MVP_SAMPLE_MAX_CHUNKS:
+ *   MVP_EUNSUPPORTED beyond, nothing is launched.  MVP_EINVAL unless Ntot, S, nb_pts >= 1, B >= 0, workspace 16-byte aligned with
+ *   workspace_bytes >= mvp_sample_scenes_workspace(Ntot, B, nb_pts) (0 for shapes the call refuses).  The scratch is reusable once the
+ *   launches have run (stream order). */
+#define MVP_SAMPLE_SCENE_MAX_PTS 65536
+int64_t mvp_sample_scenes_workspace(int64_t Ntot, int64_t B, int64_t nb_pts);
+int mvp_sample_scenes_f32(const int64_t* scene_offsets, const int64_t* scene_of_row, int64_t Ntot, int64_t S, int64_t B, int64_t nb_pts,
+                          uint64_t seed, const int64_t* seed_device, int64_t* choice, int32_t* num_points, void* workspace,
+                          int64_t workspace_bytes, mvp_stream_t stream);
+
+/* mvp_gather_cloud_f32: a `choice` of either sampler as the 3D baselines' network inputs, one launch.
+ *   points (Ntot,3) float32; seg_label (Ntot,) int64 or NULL; colors (Ntot,3) uint8 or NULL; scene_offsets (S+1,), scene_of_row (B,),
+ *   choice (B,nb_pts) int64; rot (B,3,3) float32 or NULL.  Slot s of row b reads store row j = scene_offsets[scene] + choice[b,s], the
+ *   scene's slice cut to [0, Ntot] and choice clamped into the scene (64-bit addressing: 3 * Ntot may exceed 2^31).
+ *   out_points[b,a,s]  = (R[a,0]*x + R[a,1]*y) + R[a,2]*z in float32, each operation rounded once, never contracted -- `points @ R.T` of
+ *                        transforms.py:78-85 with R = rot[b]; rot NULL: an exact copy of the bits (-0.0, NaN);
+ *   out_label[b,s]     = seg_label[j];
+ *   out_feature[b,c,s] = (float)colors[j,c] / 255.0f, an IEEE division: `colors.astype(np.float32) / 255.` (scannet_3d.py:82, :185).
+ *   (B,3,nb_pts), (B,nb_pts), (B,3,nb_pts), channel-major as PN2SSG reads them; an absent input's output is not written (may be NULL).
+ *   A row whose scene has no points: zeros, label -100.
+ * MVP_EINVAL unless Ntot, S, nb_pts >= 1, B >= 0; MVP_EUNSUPPORTED for nb_pts >= 2^31 or B > MVP_SAMPLE_MAX_CHUNKS. */
+int mvp_gather_cloud_f32(const float* points, const int64_t* seg_label, const uint8_t* colors, const int64_t* scene_offsets,
+                         const int64_t* scene_of_row, const int64_t* choice, const float* rot, int64_t Ntot, int64_t S, int64_t B,
+                         int64_t nb_pts, float* out_points, int64_t* out_label, float* out_feature, mvp_stream_t stream);
+
 /* ---- ragged scenes: the whole-scene chunker and the packing of its chunks (NEW on the device) ----
  * scene2chunks_legacy (mvpnet/utils/chunk_util.py:4-53) for all sliding windows of a scene, as index lists in CSR form instead of
  * (windows x points) membership matrices.  points (n,3) float32; corners (nc,2) float32: the windows' lower xy corners, computed by the

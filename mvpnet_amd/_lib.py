@@ -138,6 +138,8 @@ _SIGNATURES = {
     'mvp_select_frames_u32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
     'mvp_select_frames_ranges_u32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
     'mvp_sample_chunks_f32': [_ptr] * 6 + [_i64] * 6 + [ctypes.c_double] * 5 + [ctypes.c_int, ctypes.c_uint64] + [_ptr] * 9 + [_i64, _ptr],
+    'mvp_sample_scenes_f32': [_ptr, _ptr] + [_i64] * 4 + [ctypes.c_uint64] + [_ptr] * 4 + [_i64, _ptr],
+    'mvp_gather_cloud_f32': [_ptr] * 7 + [_i64] * 4 + [_ptr] * 4,
     'mvp_scene_chunks_count_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _ptr],
     'mvp_scene_chunks_fill_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr],
     'mvp_pack_chunks_f32': [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _ptr, _i64, _ptr],
@@ -159,7 +161,7 @@ _SIGNATURES['mvp_mlp_weight_grad_finish_act_p_f32'] = [_ptr] * 6 + [ctypes.c_int
                                                         ctypes.c_int, _ptr]
 _SIGNATURES['mvp_mlp_input_grad_wide_p_f32'] = [_ptr] * 8 + [ctypes.c_int, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64,
                                                  ctypes.c_int, ctypes.c_int, _ptr]
-EXPORTS = ['mvp_version', 'mvp_strerror', 'mvp_lift_workspace_bytes', 'mvp_ball_query_grid_workspace', 'mvp_knn3_grid_workspace', 'mvp_vote_nearest_workspace', 'mvp_sample_chunks_workspace', 'mvp_prepare_frames_workspace', 'mvp_mlp_weight_grad_workspace_floats', 'mvp_mlp_input_grad_wide_workspace_bytes', 'mvp_group_lin_partial_count', 'mvp_colstats_partial_count',
+EXPORTS = ['mvp_version', 'mvp_strerror', 'mvp_lift_workspace_bytes', 'mvp_ball_query_grid_workspace', 'mvp_knn3_grid_workspace', 'mvp_vote_nearest_workspace', 'mvp_sample_chunks_workspace', 'mvp_sample_scenes_workspace', 'mvp_prepare_frames_workspace', 'mvp_mlp_weight_grad_workspace_floats', 'mvp_mlp_input_grad_wide_workspace_bytes', 'mvp_group_lin_partial_count', 'mvp_colstats_partial_count',
            'mvp_set_mlp_precision', 'mvp_get_mlp_precision', 'mvp_mlp_layer_backward_partial_count', 'mvp_set_mlp_stream', 'mvp_set_mlp_precision_backward', 'mvp_get_mlp_precision_backward', 'mvp_mlp_precision_scope', 'mvp_set_fps_mode', 'mvp_fps_debug_spin_limit', 'mvp_fps_last_kernel'] + sorted(_SIGNATURES)
 
 
@@ -184,6 +186,8 @@ def lib():
         handle.mvp_vote_nearest_workspace.argtypes = [_i64, _i64]
         handle.mvp_sample_chunks_workspace.restype = ctypes.c_int64
         handle.mvp_sample_chunks_workspace.argtypes = [_i64, _i64, _i64, _i64]
+        handle.mvp_sample_scenes_workspace.restype = ctypes.c_int64
+        handle.mvp_sample_scenes_workspace.argtypes = [_i64, _i64, _i64]
         handle.mvp_prepare_frames_workspace.restype = ctypes.c_size_t
         handle.mvp_prepare_frames_workspace.argtypes = [_i64]
         handle.mvp_group_lin_partial_count.restype = ctypes.c_int64

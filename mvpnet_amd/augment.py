@@ -9,7 +9,13 @@ pixel ids / feature rows (mvp_lift_aug_f32), the rotation acts on `points` and t
 
 `color_jitter` (scannet_2d3d.py:241-243, T.ColorJitter on the PIL image) is applied by ops.prepare_frames to the frames picked from a
 raw uint8 store; `draw_color_jitter` / `draw_flip` below make its draws ON THE DEVICE (torchvision's law, not its draws), which is how
-scene.sample_train_batch builds a jittered, mirrored batch without a host synchronisation.  DeviceAugmentation does not touch colours."""
+scene.sample_train_batch builds a jittered, mirrored batch without a host synchronisation.  DeviceAugmentation does not touch colours.
+
+The 3D baselines rotate by another law (mvpnet/data/transforms.py:64-92, `RandomRotateZ`): an angle uniform in RADIANS, a float32 matrix,
+applied to `points` as `v @ R.T` in float32 before the network.  `draw_z_rotation` draws those matrices on the device; ops.gather_cloud
+applies them (scene.sample_train_batch_3d)."""
+import math
+
 import numpy as np
 import torch
 
@@ -93,3 +99,20 @@ def draw_flip(n, p, device, generator=None):
     """n (an int or a shape) horizontal-flip flags as uint8 on `device`: 1 with probability p (`np.random.rand() < flip`,
     scannet_2d3d.py:293), drawn on the device."""
     return (torch.rand(_shape(n), dtype=torch.float64, generator=generator, device=device) < float(p)).to(torch.uint8)
+
+
+def z_rotation_from_angle(angle):
+    """angle (...,) float64 radians -> (...,3,3) float32 [[c,-s,0],[s,c,0],[0,0,1]]: c and s computed in float64 and rounded once, the
+    matrix `Rotation.from_rotvec(angle * (0,0,1)).as_dcm().astype(np.float32)` of transforms.py:73-76 up to that rounding."""
+    angle = angle.double()
+    c, s = torch.cos(angle), torch.sin(angle)
+    zero, one = torch.zeros_like(c), torch.ones_like(c)
+    return torch.stack([c, -s, zero, s, c, zero, zero, zero, one], dim=-1).view(angle.shape + (3, 3)).float().contiguous()
+
+
+def draw_z_rotation(n, low=-math.pi, high=math.pi, device=None, generator=None):
+    """n (an int or a shape) rotations about z by `transforms.RandomRotate`'s law (mvpnet/data/transforms.py:68-76; RandomRotateZ's defaults),
+    drawn on `device` without a host synchronisation: angle = low + (high - low) * u with u uniform in [0, 1) in float64 (numpy's
+    uniform(low, high)), -> n + (3,3) float32 (z_rotation_from_angle).  generator: one of `device`, or None for its global generator."""
+    u = torch.rand(_shape(n), dtype=torch.float64, generator=generator, device=device)
+    return z_rotation_from_angle(float(low) + (float(high) - float(low)) * u)

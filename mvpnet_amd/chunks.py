@@ -138,6 +138,20 @@ def sample_train_chunks(points, seg_label, scene_offsets, scene_of_chunk, nb_pts
     return out
 
 
+def sample_train_scenes(scene_offsets, scene_of_row, nb_pts, Ntot=None, generator=None):
+    """`CropPad(nb_pts)` of B whole scenes drawn on the device: what `ScanNet3DScene.__getitem__` does with the transform of
+    configs/scannet/3d_baselines/pn2ssg_scene.yaml (mvpnet/data/scannet_3d.py:206-221, mvpnet/data/transforms.py:112-133) for B dataset
+    indices at once, without a host synchronisation -- sample_train_chunks' sibling, where crop_pad_choice needs every n on the host.
+    scene_offsets (S+1,) int64 and scene_of_row (B,) int64 on the device; Ntot: the store's point count (ops.sample_scenes).  The
+    resampling seed is drawn ON THE DEVICE from `generator` (a generator of that device, or its global one): the reference's law, not
+    its draws.  -> ops.sample_scenes' dict (choice (B,nb_pts) int64, num_points (B,) int32) + seed (1,) int64 on the device."""
+    from . import ops
+    seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=generator, device=scene_offsets.device)
+    out = ops.sample_scenes(scene_offsets, scene_of_row, nb_pts, seed=seed, Ntot=Ntot)
+    out['seed'] = seed
+    return out
+
+
 def _kinv_of(cam_matrix):
     """inverse of the 3x3 intrinsics in float32 on the host, as the loader does it (np.linalg.inv(cam_matrix[:3, :3]), scannet_2d3d.py:38)."""
     cam = cam_matrix.detach().cpu().numpy() if torch.is_tensor(cam_matrix) else np.asarray(cam_matrix)

@@ -205,6 +205,31 @@ def build_color_jitter(cfg, training=True):
     return tuple(float(v) for v in jitter) if jitter else ()
 
 
+def build_batch_3d(cfg, training=True):
+    """A 3D-baseline config (configs/scannet/3d_baselines/*.yaml) as the keyword arguments of scene.sample_train_batch_3d: DATASET.TYPE and
+    its node (mvpnet/data/build.py:45-70) + {TRAIN,VAL}.AUGMENTATION (parse_augmentations, :73-83).  Exactly (("CropPad", n),) with or
+    without a bare "RandomRotateZ" behind it is accepted -- the transform lists the four YAMLs use; anything else raises ValueError.
+    -> dict: dataset, nb_pts, use_color, z_rot ((-pi, pi), RandomRotateZ's defaults, or None) [, chunk_size, chunk_margin, chunk_thresh]."""
+    import math
+    assert cfg.TASK == 'sem_seg_3d', cfg.TASK
+    dataset = cfg.DATASET.TYPE
+    if dataset not in ('ScanNet3DChunks', 'ScanNet3DScene'):
+        raise ValueError('build_batch_3d: DATASET.TYPE {!r} is not a 3D-baseline dataset'.format(dataset))
+    aug = (cfg.TRAIN if training else cfg.VAL).AUGMENTATION
+    aug = tuple(aug) if isinstance(aug, (tuple, list)) else (aug,)
+    ok = 1 <= len(aug) <= 2 and isinstance(aug[0], (tuple, list)) and len(aug[0]) == 2 and aug[0][0] == 'CropPad' \
+        and isinstance(aug[0][1], int) and not isinstance(aug[0][1], bool) and aug[0][1] >= 1 and (len(aug) == 1 or aug[1] == 'RandomRotateZ')
+    if not ok:
+        raise ValueError('build_batch_3d: AUGMENTATION must be (("CropPad", n),) or (("CropPad", n), "RandomRotateZ"), not {!r}'.format(aug))
+    node = cfg.DATASET.get(dataset, {})
+    kwargs = {'dataset': dataset, 'nb_pts': aug[0][1], 'use_color': bool(node.get('use_color', False)),
+              'z_rot': (-math.pi, math.pi) if len(aug) == 2 else None}
+    if dataset == 'ScanNet3DChunks':
+        kwargs.update(chunk_size=tuple(node.get('chunk_size', (1.5, 1.5))), chunk_margin=tuple(node.get('chunk_margin', (0.2, 0.2))),
+                      chunk_thresh=node.get('chunk_thresh', 0.3))
+    return kwargs
+
+
 def build_optimizer(cfg, model):
     """common/solver/build.py:7-22"""
     import torch

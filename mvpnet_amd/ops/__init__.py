@@ -10,12 +10,13 @@ from .lifting import unproject, pixel_knn, lift_gather, lift, rotate_rows
 from .overlap import rgbd_overlap, select_frames_batched, pack_bits, unpack_bits
 from .vote import vote_nearest
 from .sample import sample_chunks
+from .scene_sample import sample_scenes, gather_cloud
 from .chunker import scene_chunks, pack_chunks
 from .frames import prepare_frames
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
            'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
-           'pack_bits', 'unpack_bits', 'vote_nearest', 'sample_chunks', 'scene_chunks', 'pack_chunks',
+           'pack_bits', 'unpack_bits', 'vote_nearest', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
            'prepare_frames']
 
 

@@ -373,3 +373,40 @@ def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k, *, color
             'cam_matrix': store['cam'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
             'kinv': store['kinv'][scene_of_chunk][:, None].expand(B, nv, 3, 3).contiguous(),
             'pixel_box': torch.cat([box[:, :2] - 0.1, box[:, 2:] + 0.1], dim=1), 'k': int(k)}
+
+
+def sample_train_batch_3d(store, scene_of_row, *, dataset, nb_pts, use_color=False, z_rot=None, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2),
+                          chunk_thresh=0.3, num_tries=10, generator=None):
+    """One batch of a 3D baseline (configs/scannet/3d_baselines/*.yaml) from scenes resident on the device: what a batch of
+    `ScanNet3DChunks.__getitem__` / `ScanNet3DScene.__getitem__` calls with the transform `CropPad(nb_pts)` [+ `RandomRotateZ`] collates to
+    (mvpnet/data/scannet_3d.py:135-221, mvpnet/data/transforms.py:64-133), without a host synchronisation.
+    store: dict of device tensors -- points (Ntot,3) float32, seg_label (Ntot,) int64 (mapped, negative = unlabelled), scene_offsets (S+1,)
+        int64: the scenes, one after the other; colors (Ntot,3) uint8 for use_color.
+    scene_of_row (B,) int64 on the device: the dataset indices of the batch.
+    dataset: 'ScanNet3DChunks' -- chunks.sample_train_chunks(..., bounds_f64=True) draws a chunk per row (chunk_size, chunk_margin,
+        chunk_thresh, num_tries: the YAML's DATASET.ScanNet3DChunks; nb_pts <= 8192) -- or 'ScanNet3DScene' -- chunks.sample_train_scenes
+        crops or pads the whole scene (nb_pts <= 65536; the chunk arguments are not used).  ops.gather_cloud then reads the store once.
+    z_rot: None -- the validation recipe, points are copied -- or (low, high) in radians, RandomRotateZ's (-pi, pi): one matrix per row
+        (augment.draw_z_rotation), applied as `points @ R.T` in float32.
+    All draws come from `generator`, in this order: the sampler's (ScanNet3DChunks: the centres, then the seed; ScanNet3DScene: the
+    seed), then the angles.
+    -> what PN2SSG and SegLoss read: points (B,3,nb_pts) float32, seg_label (B,nb_pts) int64 [, feature (B,3,nb_pts) float32 = colors / 255]
+    + the draws: choice (B,nb_pts) int64 inside each row's scene [, z_rot (B,3,3) float32]."""
+    from . import augment as A
+    points, offsets = store['points'], store['scene_offsets']
+    if dataset == 'ScanNet3DChunks':
+        choice = CH.sample_train_chunks(points, store['seg_label'], offsets, scene_of_row, nb_pts, chunk_size=chunk_size, chunk_margin=chunk_margin,
+                                        chunk_thresh=chunk_thresh, num_tries=num_tries, bounds_f64=True, generator=generator)['choice']
+    elif dataset == 'ScanNet3DScene':
+        choice = CH.sample_train_scenes(offsets, scene_of_row, nb_pts, Ntot=points.size(0), generator=generator)['choice']
+    else:
+        raise ValueError("sample_train_batch_3d: dataset must be 'ScanNet3DChunks' or 'ScanNet3DScene', not {!r}".format(dataset))
+    rot = None
+    if z_rot is not None:
+        low, high = z_rot
+        rot = A.draw_z_rotation(scene_of_row.numel(), low, high, device=points.device, generator=generator)
+    out = ops.gather_cloud(points, offsets, scene_of_row, choice, seg_label=store['seg_label'], colors=store['colors'] if use_color else None, rot=rot)
+    out['choice'] = choice
+    if rot is not None:
+        out['z_rot'] = rot
+    return out
