@@ -477,6 +477,46 @@ int mvp_prepare_frames_u8(const uint8_t* frames, int64_t Ftot, int64_t H, int64_
                           const uint8_t* order, const uint8_t* flip, const float* mean_std, int channels_last, float* out, void* workspace,
                           mvp_stream_t stream);
 
+/* ---- resize and label maps (NEW on the device; the reference calls Pillow per frame in a data-loader worker) ----
+ * `image.resize(size, Image.BILINEAR)` on uint8 RGB and `label.resize(size, Image.NEAREST)` on a 16-bit label image
+ * (mvpnet/data/scannet_2d.py:153-156, mvpnet/data/scannet_2d3d.py:234-239), bit-identical to Pillow.
+ *
+ * Host tables, in double, no GPU (Pillow's precompute_coeffs + normalize_coeffs_8bpc for the triangle filter), one axis inS -> outS:
+ *   scale = inS / outS, fs = max(scale, 1), support = fs, ksize = ceil(support) * 2 + 1; per output xx: center = (xx + 0.5) * scale,
+ *   xmin = max((int)(center - support + 0.5), 0), count = min((int)(center + support + 0.5), inS) - xmin; weights
+ *   max(0, 1 - |(x + xmin - center + 0.5) * (1 / fs)|) for x < count, summed in index order and divided by the sum; integer weights
+ *   (int)(w * 2^22 + 0.5) for w >= 0, (int)(w * 2^22 - 0.5) below; entries behind count are 0.
+ * mvp_resize_bilinear_table writes xmin (outS), count (outS), coef (outS * ksize) and *ksize; with the three arrays NULL only *ksize.
+ * mvp_resize_nearest_table writes index[x] = min((int)(scale * (x + 0.5)), inS - 1): the rule Pillow applies to 16-bit ("I;16")
+ * images, which is what ScanNet's label PNGs are (its 8-bit and float modes accumulate the coordinate instead; not reproduced: the
+ * reference never resizes such an image with NEAREST).  MVP_EINVAL unless inS, outS >= 1; MVP_EUNSUPPORTED for sizes of 2^31 and more. */
+int mvp_resize_bilinear_table(int64_t inS, int64_t outS, int32_t* xmin, int32_t* count, int32_t* coef, int32_t* ksize);
+int mvp_resize_nearest_table(int64_t inS, int64_t outS, int32_t* index);
+
+/* frames (Ftot,H,W,3) uint8; picked (Nf,) int64 global rows, clamped to [0, Ftot) -> out (Nf,h,w,3) uint8: the picked frames resized.
+ * xtab / ytab ON THE DEVICE: an axis' table as int32 [xmin (outS) | count (outS) | coef (outS * ksize)], W -> w and H -> h; NULL exactly
+ * when that axis keeps its size.  Pillow's two passes in Pillow's order, each clip8((2^21 + sum pixel * coef) >> 22) in 32-bit integers
+ * (255 * 2^22 < 2^31), no floating point: horizontal first, ITS RESULT ROUNDED TO uint8, then vertical.  One launch (per 65535 frames):
+ * a workgroup owns a tile of 8 x 32 output pixels and keeps the intermediate rows its tile draws on in LDS (18 KiB); with one table
+ * NULL only the other pass runs, with both NULL the frames are copied.  A table's contents are the caller's: windows are clamped into
+ * the image, a wrong table gives wrong pixels and no stray read.
+ * Accepted sizes: at most 64 taps per changed axis (inS / outS <= 31) and, when both axes change, a tile's
+ * ceil(7 * H/h + 2 * max(H/h, 1)) + 2 input rows <= 192 (H / h up to ~21): 1296x968 -> 160x120 (ksize 19 on both axes, 75 rows), 640x480 ->
+ * 160x120 (ksize 9, 38 rows) and every enlargement fit.  MVP_EUNSUPPORTED beyond, and for an image of 2^31 bytes or more; MVP_EINVAL for a
+ * size < 1, Nf < 1 or a table that is NULL for a changed axis / given for an unchanged one.  Nothing is launched on an error. */
+int mvp_resize_frames_u8(const uint8_t* frames, int64_t Ftot, int64_t H, int64_t W, const int64_t* picked, int64_t Nf, int64_t h, int64_t w,
+                         const int32_t* xtab, const int32_t* ytab, uint8_t* out, mvp_stream_t stream);
+
+/* labels (Ftot,H,W) uint16 raw ids as a label PNG decodes; picked (Nf,) as above -> out (Nf,h,w) int64, one launch:
+ *   raw = labels[picked[f], yi[y], xi[flip[f] ? w - 1 - x : x]];  out = mapping ? (raw < T ? mapping[raw] : ignore_value) : raw
+ * (`label.resize(size, Image.NEAREST)`, F.hflip, `label_mapping[label]`: scannet_2d.py:156, :163, :167-168; a raw id beyond the table
+ * raises there, here it is ignored).  yi (h) / xi (w) int32 ON THE DEVICE (mvp_resize_nearest_table), clamped into the image; NULL =
+ * identity, for h == H / w == W only.  flip (Nf,) uint8 or NULL; mapping (T,) int64 on the device or NULL.
+ * MVP_EINVAL for a size < 1, Nf < 1, a NULL table for a changed axis or T < 0; MVP_EUNSUPPORTED for H*W or h*w >= 2^31. */
+int mvp_prepare_labels_u16(const uint16_t* labels, int64_t Ftot, int64_t H, int64_t W, const int64_t* picked, int64_t Nf, int64_t h, int64_t w,
+                           const int32_t* yi, const int32_t* xi, const uint8_t* flip, const int64_t* mapping, int64_t T, int64_t ignore_value,
+                           int64_t* out, mvp_stream_t stream);
+
 /* Column slices of several row-major float matrices in one launch (host-side helper of the shared-MLP path: the reference slices
  * nothing -- it concatenates the inputs instead, modules.py:32-35,178-186 -- the linear-first factorisation of those layers needs
  * each column group of the weight as its own aligned operand).  table: n x 6 int64 ON THE DEVICE, per entry

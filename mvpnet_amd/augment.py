@@ -101,6 +101,13 @@ def draw_flip(n, p, device, generator=None):
     return (torch.rand(_shape(n), dtype=torch.float64, generator=generator, device=device) < float(p)).to(torch.uint8)
 
 
+def draw_frames(n, Ftot, device, generator=None):
+    """n (an int or a shape) frame rows uniform in [0, Ftot) as int64 on `device`, without a host synchronisation: for callers of
+    scene.sample_train_batch_2d that have no sampler of their own.  The rows are drawn WITH replacement, every batch on its own; the
+    reference shuffles an epoch (a DataLoader with shuffle=True over ScanNet2D: every frame once per epoch, without replacement)."""
+    return torch.randint(0, int(Ftot), _shape(n), dtype=torch.int64, generator=generator, device=device)
+
+
 def z_rotation_from_angle(angle):
     """angle (...,) float64 radians -> (...,3,3) float32 [[c,-s,0],[s,c,0],[0,0,1]]: c and s computed in float64 and rounded once, the
     matrix `Rotation.from_rotvec(angle * (0,0,1)).as_dcm().astype(np.float32)` of transforms.py:73-76 up to that rounding."""

@@ -1,8 +1,9 @@
 """Minimal configuration + factory layer so the reference's experiment YAMLs drive this package unmodified
-(`configs/scannet/mvpnet_3d_unet_resnet34_pn2ssg.yaml`, `configs/scannet/3d_baselines/pn2ssg_chunk.yaml`).
+(`configs/scannet/mvpnet_3d_unet_resnet34_pn2ssg.yaml`, `configs/scannet/3d_baselines/pn2ssg_chunk.yaml`,
+`configs/scannet/unet_resnet34.yaml`).
 
 The reference uses yacs (absent here): defaults in `common/config/base.py:10-137`, task defaults in
-`mvpnet/config/mvpnet_3d.py:6-80` / `mvpnet/config/sem_seg_3d.py`, `purge_cfg` in
+`mvpnet/config/mvpnet_3d.py:6-80` / `mvpnet/config/sem_seg_3d.py` / `mvpnet/config/sem_seg_2d.py`, `purge_cfg` in
 `common/config/__init__.py:4-17`, factories in `mvpnet/models/build.py:8-47` and
 `common/solver/build.py:7-41`.  This is a PyYAML + `ast.literal_eval` work-alike of exactly what those
 need: nested attribute access, defaults, `merge_from_file` / `merge_from_list`, tuples written as strings
@@ -125,6 +126,18 @@ def get_cfg_sem_seg_3d():
     return cfg
 
 
+def get_cfg_sem_seg_2d():
+    """mvpnet/config/sem_seg_2d.py (the 2D stage: UNetResNet34 on single frames, train_2d.py)"""
+    cfg = _base()
+    cfg.merge(CfgNode._convert({
+        'TASK': 'sem_seg_2d', 'VAL': {'METRIC': 'seg_iou'},
+        'DATASET': {'ROOT_DIR': '', 'TRAIN': '', 'VAL': '',
+                    'ScanNet2D': {'resize': '()', 'normalizer': '((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))',
+                                  'augmentation': {'flip': 0.0, 'color_jitter': '()'}}},
+        'MODEL': {'TYPE': '', 'UNetResNet34': {'num_classes': 20, 'p': 0.0}}}))
+    return cfg
+
+
 def load_cfg(path=None, text=None, opts=()):
     """Defaults of the YAML's TASK + the YAML + `KEY VALUE` overrides, purged like the reference does."""
     raw = CfgNode()
@@ -133,7 +146,7 @@ def load_cfg(path=None, text=None, opts=()):
     if text is not None:
         raw.merge_from_text(text)
     task = raw.get('TASK', 'mvpnet_3d')
-    cfg = {'mvpnet_3d': get_cfg_mvpnet_3d, 'sem_seg_3d': get_cfg_sem_seg_3d}[task]()
+    cfg = {'mvpnet_3d': get_cfg_mvpnet_3d, 'sem_seg_3d': get_cfg_sem_seg_3d, 'sem_seg_2d': get_cfg_sem_seg_2d}[task]()
     cfg.merge(raw)
     cfg.merge_from_list(list(opts))
     purge_cfg(cfg)
@@ -155,6 +168,62 @@ def build_model_sem_seg_3d(cfg):
     from .pn2 import PN2SSG
     assert cfg.TASK == 'sem_seg_3d' and cfg.MODEL.TYPE == 'PN2SSG', (cfg.TASK, cfg.MODEL.TYPE)
     return PN2SSG(**dict(cfg.MODEL.get('PN2SSG', {})))
+
+
+def build_model_sem_seg_2d(cfg):
+    """mvpnet/models/build.py (sem_seg_2d) / mvpnet/models/unet_resnet34.py:127-139 -> model (loss: build_loss_2d)"""
+    from .unet_resnet34 import UNetResNet34
+    assert cfg.TASK == 'sem_seg_2d' and cfg.MODEL.TYPE == 'UNetResNet34', (cfg.TASK, cfg.MODEL.TYPE)
+    return UNetResNet34(**dict(cfg.MODEL.get('UNetResNet34', {})))
+
+
+def build_loss_2d(cfg):
+    """mvpnet/models/unet_resnet34.py:127-139: SegLoss, with the class weights of TRAIN.LABEL_WEIGHTS_PATH (np.loadtxt, float32) when the
+    path is non-empty."""
+    import numpy as np
+    import torch
+    from .mvpnet3d import SegLoss
+    path = cfg.TRAIN.get('LABEL_WEIGHTS_PATH', '')
+    weight = torch.from_numpy(np.loadtxt(path, dtype=np.float32)) if path else None
+    if weight is not None and torch.cuda.is_available():
+        weight = weight.cuda()  # (as the reference does: the loss then makes no host-to-device copy per step)
+    return SegLoss(weight=weight)
+
+
+def build_batch_2d(cfg, training=True):
+    """The 2D config (configs/scannet/unet_resnet34.yaml) as the keyword arguments of scene.sample_train_batch_2d: DATASET.ScanNet2D's
+    resize and normalizer; its augmentation (color_jitter, flip) for the training split only (mvpnet/data/build.py passes the
+    augmentation to the training split only).  -> dict: resize ((w, h) or None), image_normalizer, color_jitter, flip."""
+    assert cfg.TASK == 'sem_seg_2d', cfg.TASK
+    if cfg.DATASET.TYPE != 'ScanNet2D':
+        raise ValueError('build_batch_2d: DATASET.TYPE {!r} is not the 2D dataset'.format(cfg.DATASET.TYPE))
+    node = cfg.DATASET.get('ScanNet2D', {})
+    aug = node.get('augmentation', {}) if training else {}
+    resize, normalizer, jitter = node.get('resize', ()), node.get('normalizer', ()), aug.get('color_jitter', ())
+    return {'resize': tuple(int(v) for v in resize) if resize else None,
+            'image_normalizer': tuple(tuple(float(v) for v in part) for part in normalizer) if normalizer else None,
+            'color_jitter': tuple(float(v) for v in jitter) if jitter else (), 'flip': float(aug.get('flip', 0.0))}
+
+
+def scannet_label_mapping(tsv_path, labelids_path, ignore_value=-100):
+    """The `raw_to_scannet` table of mvpnet/data/scannet_2d.py:86-103 as a (T,) int64 tensor (on the host: move it to the store's device
+    once): raw ScanNet id -> nyu40 id (the columns `id` and `nyu40id` of scannetv2-labels.combined.tsv, ids the file does not list -> 0)
+    -> the position of that nyu40 id in labelids.txt (20 classes), ignore_value for every other one.  What ops.prepare_labels and
+    scene.sample_train_batch_2d take as `mapping` / `label_mapping`."""
+    import csv
+    import torch
+    with open(tsv_path) as f:
+        pairs = [(int(row['id']), int(row['nyu40id'])) for row in csv.DictReader(f, delimiter='\t')]
+    raw_to_nyu40 = [0] * (max(k for k, _ in pairs) + 1)
+    for k, v in pairs:
+        raw_to_nyu40[k] = v
+    with open(labelids_path) as f:
+        class_ids = [int(line.rstrip().split('\t')[0]) for line in f.readlines()]
+    assert len(class_ids) == 20, len(class_ids)
+    nyu40_to_scannet = [int(ignore_value)] * 41
+    for position, class_id in enumerate(class_ids):
+        nyu40_to_scannet[class_id] = position
+    return torch.tensor([nyu40_to_scannet[v] for v in raw_to_nyu40], dtype=torch.int64)
 
 
 def build_model_mvpnet_3d(cfg, net_2d=None, load_2d_ckpt=True, freeze_2d=True):

@@ -21,7 +21,10 @@ from . import _lib as L
 
 def confusion_matrix(seg_logit, seg_label, num_classes=None, ignore_index=-100, out=None):
     """(C,C) int64 matrix [label][argmax logit] over the points whose label is not ignore_index, added to `out` if given.
-    seg_logit (B,C,N) in any strides that keep (b,c,n) addressable (e.g. the transposed view of channels-last rows)."""
+    seg_logit (B,C,N) in any strides that keep (b,c,n) addressable (e.g. the transposed view of channels-last rows), or the 2D stage's
+    (B,C,H,W) with seg_label (B,H,W): viewed as (B,C,H*W), without a copy for contiguous and channels-last memory."""
+    if seg_logit.dim() == 4:
+        seg_logit, seg_label = seg_logit.flatten(2), seg_label.reshape(seg_label.size(0), -1)
     B, C, N = seg_logit.shape
     n = C if num_classes is None else num_classes
     mat = out if out is not None else torch.zeros((n, n), dtype=torch.int64, device=seg_logit.device)

@@ -215,8 +215,9 @@ class _SegLossFn(torch.autograd.Function):
 
 class SegLoss(nn.Module):
     """Weighted cross entropy with ignore_index (loss.py:5-21).  fp32 (B,C,N) logits on the GPU go through the fused HIP
-    kernels (logits in any strides); everything else (host tensors, other dtypes / ranks) through F.cross_entropy, which is
-    what the reference calls."""
+    kernels (logits in any strides), and so do the 2D stage's (B,C,H,W) logits with (B,H,W) labels, contiguous or channels-last: they
+    are VIEWED as (B,C,H*W) -- both layouts merge H and W without a copy -- and the gradient comes back in the logits' own layout;
+    everything else (host tensors, other dtypes / ranks) through F.cross_entropy, which is what the reference calls."""
 
     def __init__(self, weight=None, ignore_index=-100):
         super().__init__()
@@ -225,6 +226,9 @@ class SegLoss(nn.Module):
 
     def forward(self, preds, labels):
         logit, label = preds['seg_logit'], labels['seg_label']
+        if logit.is_cuda and logit.dtype == torch.float32 and logit.dim() == 4 and label.dim() == 3 and label.dtype == torch.int64:
+            # (B,C,H,W) -> (B,C,H*W): a view for contiguous and channels-last memory alike (stride(H) == W * stride(W))
+            logit, label = logit.flatten(2), label.reshape(label.size(0), -1)
         if logit.is_cuda and logit.dtype == torch.float32 and logit.dim() == 3 and label.dtype == torch.int64:
             weight = None if self.weight is None else self.weight.to(device=logit.device, dtype=torch.float32).contiguous()
             loss = _SegLossFn.apply(logit, label.contiguous(), weight, self.ignore_index)

@@ -13,11 +13,12 @@ from .sample import sample_chunks
 from .scene_sample import sample_scenes, gather_cloud
 from .chunker import scene_chunks, pack_chunks
 from .frames import prepare_frames
+from .resize import resize_frames, prepare_labels
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
            'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
            'pack_bits', 'unpack_bits', 'vote_nearest', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
-           'prepare_frames']
+           'prepare_frames', 'resize_frames', 'prepare_labels']
 
 
 def as_point_major(x, transpose):

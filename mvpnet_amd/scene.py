@@ -375,6 +375,50 @@ def assemble_train_batch(store, scene_of_chunk, ch, num_rgbd_frames, k, *, color
             'pixel_box': torch.cat([box[:, :2] - 0.1, box[:, 2:] + 0.1], dim=1), 'k': int(k)}
 
 
+def sample_train_batch_2d(store, picked, *, resize=None, color_jitter=(), image_normalizer=None, flip=0.0, label_mapping=None, channels_last=False,
+                          generator=None):
+    """One batch of the 2D stage (configs/scannet/unet_resnet34.yaml, train_2d.py) from frames resident on the device: what a batch of
+    `ScanNet2D.__getitem__` calls collates to (mvpnet/data/scannet_2d.py:146-181), without a host synchronisation.
+    store: dict of device tensors -- images (Ftot,H,W,3) uint8 RGB and labels (Ftot,H,W) uint16 raw ids, as the PNGs decode.
+    picked (B,) int64 on the device: the frames of the batch (a sampler's, or augment.draw_frames').
+    The reference's order: resize -> jitter -> flip -> `/ 255.` -> normalise.  resize: the YAML's (w, h) or None; when it differs from the
+    store's size, ops.resize_frames (Pillow's BILINEAR, bit for bit) makes the uint8 frames of that size and the labels are read through
+    Pillow's NEAREST indices; ops.prepare_frames then runs on those frames with color_jitter = the YAML's (brightness, contrast,
+    saturation) (augment.draw_color_jitter), flip = the probability of mirroring a frame (augment.draw_flip) and image_normalizer = the
+    YAML's (mean, std); ops.prepare_labels gets the SAME flip draw and label_mapping ((T,) int64 on the device:
+    config.scannet_label_mapping; None keeps the raw ids).  channels_last: images with (B,h,w,3) memory.  All draws come from
+    `generator`, in this order: jitter, flip.
+    -> {'image': (B,3,h,w) float32, 'seg_label': (B,h,w) int64}: what UNetResNet34 and SegLoss read."""
+    from . import augment as A
+    images, labels = store['images'], store['labels']
+    if images.dim() != 4 or labels.dim() != 3 or tuple(labels.shape) != tuple(images.shape[:3]):
+        raise RuntimeError('sample_train_batch_2d: images (Ftot,H,W,3) uint8 and labels (Ftot,H,W) uint16 must describe the same frames')
+    if picked.dim() != 1:
+        raise RuntimeError('sample_train_batch_2d: picked must be (B,)')
+    H, W = images.size(1), images.size(2)
+    size = None if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (W, H) else (int(resize[0]), int(resize[1]))
+    dev, B = images.device, picked.numel()
+    factor, order = A.draw_color_jitter(B, color_jitter, dev, generator=generator) if color_jitter else (None, None)
+    flips = A.draw_flip(B, flip, dev, generator=generator) if flip else None
+    if size is None:
+        image = ops.prepare_frames(images, picked, factor=factor, order=order, flip=flips, normalizer=image_normalizer, channels_last=channels_last)
+    else:
+        small = ops.resize_frames(images, picked, size)
+        image = ops.prepare_frames(small, _arange(B, dev), factor=factor, order=order, flip=flips, normalizer=image_normalizer,
+                                   channels_last=channels_last)
+    return {'image': image, 'seg_label': ops.prepare_labels(labels, picked, size=size, flip=flips, mapping=label_mapping)}
+
+
+_ARANGE = {}  # (device, n) -> arange(n) int64 on the device: made once, so a later batch launches nothing for it
+
+
+def _arange(n, dev):
+    t = _ARANGE.get((dev, n))
+    if t is None:
+        t = _ARANGE[(dev, n)] = torch.arange(n, dtype=torch.int64, device=dev)
+    return t
+
+
 def sample_train_batch_3d(store, scene_of_row, *, dataset, nb_pts, use_color=False, z_rot=None, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2),
                           chunk_thresh=0.3, num_tries=10, generator=None):
     """One batch of a 3D baseline (configs/scannet/3d_baselines/*.yaml) from scenes resident on the device: what a batch of
