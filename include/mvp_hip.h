@@ -686,6 +686,38 @@ int mvp_mlp_precision_scope(int terms, int terms_backward);
  * step >= 1 is the number of THIS update; fp32 arithmetic, the bias corrections in double on the host.  96 tensors per launch. */
 int mvp_adam_step_f32(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
                       int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, double step, mvp_stream_t stream);
+/* One SGD step of n float32 tensors (solver.hip; replaces, on the GPU, torch.optim.SGD.step of the reference's 2D stage:
+ * common/solver/build.py:7-22 with configs/scannet/unet_resnet34.yaml).  params / grads / momentum_buf: HOST arrays of n device pointers,
+ * numel their element counts (< 2^31 each), first: a HOST array of n bytes, grad_scale: NULL or a DEVICE pointer to one float (a clip
+ * coefficient that never left the device).  torch.optim.SGD semantics per element in fp32:
+ *   g' = g * grad_scale (when given: one rounded product);  g' += weight_decay p (when weight_decay != 0);
+ *   momentum != 0:  buf = g' where first[i] != 0 (torch's first step: a copy, no dampening; the buffer is not read),
+ *                   else buf = (momentum buf) + (1 - dampening) g';   g' = nesterov ? g' + momentum buf : buf;
+ *   p = p - lr g'
+ * every `x + alpha y` above is one fused multiply-add (4 roundings per element and step, not 6), momentum buf a rounded product.
+ * momentum == 0 touches no buffer (momentum_buf and first may be NULL).  Tensors on their first and on later steps share a launch (the
+ * bytes of `first` travel as a bit mask); 124 tensors per launch.  MVP_EINVAL, before any launch, for n < 0, momentum < 0, lr < 0 and
+ * for nesterov with momentum <= 0 or dampening != 0. */
+int mvp_sgd_step_f32(void* const* params, const void* const* grads, void* const* momentum_buf, const int64_t* numel, const uint8_t* first,
+                     int64_t n, double lr, double momentum, double dampening, double weight_decay, int nesterov, const float* grad_scale,
+                     mvp_stream_t stream);
+/* Global 2-norm of n float32 gradient tensors and the clip by it (solver.hip; replaces nn.utils.clip_grad_norm_ of the reference's train
+ * loops, train_2d.py:181-185), without atomics and without a host synchronisation; bit-reproducible.
+ *   mvp_grad_clip_partials_count: the number of partial sums for these element counts (one per 8192 elements of each tensor, rounded up):
+ *       sizes `partials` on the host; negative MVP_E* on bad arguments.
+ *   mvp_grad_sqnorm_partials_f32: grads is a HOST array of n device pointers; every workgroup writes the fp32 sum of the squares of its
+ *       8192 elements to its own slot of `partials` (device); n_partials_out (host, may be NULL) receives the count.
+ *   mvp_grad_clip_finish_f32: EVERY workgroup adds the n_partials partials in the same fixed order (strided over its lanes, then the
+ *       workgroup tree: all hold the same bits), then
+ *           total = sqrt(sum);  c = max_norm / (total + 1e-6);  coef = c < 1 ? c : (c is NaN ? c : 1)     (torch.clamp(c, max=1))
+ *       and multiplies its 8192 elements of grads by coef -- always, as torch does; workgroup 0 writes total and coef to the two device
+ *       floats.  grads == NULL: a one-workgroup launch that writes only the scalars (the coefficient is then applied by
+ *       mvp_sgd_step_f32's grad_scale).  max_norm < 0: no clipping, coef = 1.  With grads, n_partials must be the count of (numel, n). */
+int64_t mvp_grad_clip_partials_count(const int64_t* numel, int64_t n);
+int mvp_grad_sqnorm_partials_f32(const void* const* grads, const int64_t* numel, int64_t n, float* partials, int64_t* n_partials_out,
+                                 mvp_stream_t stream);
+int mvp_grad_clip_finish_f32(void* const* grads, const int64_t* numel, int64_t n, const float* partials, int64_t n_partials, double max_norm,
+                             float* total_norm_out, float* coef_out, mvp_stream_t stream);
 
 /* Shared-MLP layer on bfloat16 VALUES (mlp_bf16.hip; SURVEY 8b "+bf16 for gather/interp/MLP values"; uint16_t = bf16 bit patterns):
  *   Y (R, ldy)[:, :Cout] = act((X (R, ldx)[:, :Cin] . bf16_rn(W (Cout, ldw)[:, :Cin])^T + bias) * scale + shift)

@@ -79,6 +79,9 @@ _SIGNATURES = {
     'mvp_interp_rows_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
     'mvp_mlp_forward_bf16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _i64, _ptr],
     'mvp_adam_step_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64] + [ctypes.c_double] * 6 + [_ptr],
+    'mvp_sgd_step_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64] + [ctypes.c_double] * 4 + [ctypes.c_int, _ptr, _ptr],
+    'mvp_grad_sqnorm_partials_f32': [_ptr, _ptr, _i64, _ptr, _ptr, _ptr],
+    'mvp_grad_clip_finish_f32': [_ptr, _ptr, _i64, _ptr, _i64, ctypes.c_double, _ptr, _ptr, _ptr],
     'mvp_csr_build_i64': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
     'mvp_csr_build_sorted_i64': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
     'mvp_gather_rows_backward_csr_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
@@ -165,7 +168,7 @@ _SIGNATURES['mvp_mlp_weight_grad_finish_act_p_f32'] = [_ptr] * 6 + [ctypes.c_int
                                                         ctypes.c_int, _ptr]
 _SIGNATURES['mvp_mlp_input_grad_wide_p_f32'] = [_ptr] * 8 + [ctypes.c_int, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64,
                                                  ctypes.c_int, ctypes.c_int, _ptr]
-EXPORTS = ['mvp_version', 'mvp_strerror', 'mvp_lift_workspace_bytes', 'mvp_ball_query_grid_workspace', 'mvp_knn3_grid_workspace', 'mvp_vote_nearest_workspace', 'mvp_sample_chunks_workspace', 'mvp_sample_scenes_workspace', 'mvp_prepare_frames_workspace', 'mvp_mlp_weight_grad_workspace_floats', 'mvp_mlp_input_grad_wide_workspace_bytes', 'mvp_group_lin_partial_count', 'mvp_colstats_partial_count',
+EXPORTS = ['mvp_version', 'mvp_strerror', 'mvp_lift_workspace_bytes', 'mvp_ball_query_grid_workspace', 'mvp_knn3_grid_workspace', 'mvp_vote_nearest_workspace', 'mvp_sample_chunks_workspace', 'mvp_sample_scenes_workspace', 'mvp_prepare_frames_workspace', 'mvp_mlp_weight_grad_workspace_floats', 'mvp_mlp_input_grad_wide_workspace_bytes', 'mvp_group_lin_partial_count', 'mvp_colstats_partial_count', 'mvp_grad_clip_partials_count',
            'mvp_set_mlp_precision', 'mvp_get_mlp_precision', 'mvp_mlp_layer_backward_partial_count', 'mvp_set_mlp_stream', 'mvp_set_mlp_precision_backward', 'mvp_get_mlp_precision_backward', 'mvp_mlp_precision_scope', 'mvp_set_fps_mode', 'mvp_fps_debug_spin_limit', 'mvp_fps_last_kernel'] + sorted(_SIGNATURES)
 
 
@@ -202,6 +205,8 @@ def lib():
         handle.mvp_mlp_input_grad_wide_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
         handle.mvp_colstats_partial_count.restype = ctypes.c_int64
         handle.mvp_colstats_partial_count.argtypes = [_i64, _i64]
+        handle.mvp_grad_clip_partials_count.restype = ctypes.c_int64
+        handle.mvp_grad_clip_partials_count.argtypes = [_ptr, _i64]
         handle.mvp_set_mlp_precision.restype = ctypes.c_int
         handle.mvp_set_mlp_precision.argtypes = [ctypes.c_int, ctypes.c_int]
         handle.mvp_get_mlp_precision.restype = ctypes.c_int

@@ -310,6 +310,10 @@ def build_optimizer(cfg, model):
     if name == 'Adam' and not kwargs.get('amsgrad') and 'fused' not in kwargs and params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
         from .optim import FusedAdam  # a torch.optim.Adam (same state, same checkpoints) whose step is ONE launch for all parameter tensors
         return FusedAdam(params, lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY, **kwargs)
+    if name == 'SGD' and not kwargs.get('maximize') and not kwargs.get('differentiable') and 'fused' not in kwargs and 'foreach' not in kwargs \
+            and params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        from .optim import FusedSGD  # a torch.optim.SGD (same state, same checkpoints) whose step is one launch per 124 parameter tensors
+        return FusedSGD(params, lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY, **kwargs)
     if name in ('Adam', 'AdamW') and 'fused' not in kwargs and params and all(p.is_cuda for p in params):
         kwargs['fused'] = True  # ATen's multi-tensor kernel (three launches for ~80 tensors)
     return getattr(torch.optim, name)(params, lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY, **kwargs)

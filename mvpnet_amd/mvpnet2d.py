@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from . import ops
+from . import optim
 
 
 class MVPNet2D(nn.Module):
@@ -35,3 +36,25 @@ class MVPNet2D(nn.Module):
                                 pose=data_batch['pose'])
         gathered, _ = ops.lift_gather(logit_cl, None, knn)  # (B,N,k,classes)
         return {'seg_logit': gathered.mean(2).transpose(1, 2).contiguous()}
+
+
+def train_step_2d(model, loss_fn, optimizer, data_batch, scheduler=None, max_grad_norm=0.0):
+    """One iteration of the reference's 2D-stage loop (mvpnet/train_2d.py:158-185):
+    zero_grad -> forward -> loss_fn(preds, batch)['seg_loss'] -> backward -> [clip] -> step -> scheduler; -> (loss.detach(), preds).
+    With max_grad_norm > 0 and an optim.FusedSGD the clip is deferred: optim.total_grad_norm leaves its coefficient on the device and
+    the step multiplies the gradients by it as it reads them -- they are read once for the norm, once in the step and never rewritten
+    (so p.grad holds the UNclipped gradients afterwards).  Any other optimizer gets optim.clip_grad_norm_, the in-place clip."""
+    optimizer.zero_grad()
+    preds = model(data_batch)
+    loss = loss_fn(preds, data_batch)['seg_loss']
+    loss.backward()
+    if max_grad_norm > 0 and isinstance(optimizer, optim.FusedSGD):
+        _, coef = optim.total_grad_norm(model.parameters(), max_grad_norm)
+        optimizer.step(grad_scale=coef if coef.is_cuda else None)  # (no gradient at all: nothing to scale)
+    else:
+        if max_grad_norm > 0:
+            optim.clip_grad_norm_(model.parameters(), max_grad_norm)
+        optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach(), preds
