@@ -1,6 +1,7 @@
-// chunk_common.h -- what the training-chunk sampler (sample.hip) and the whole-scene chunker (chunker.hip) share: the pad rule, the
+// chunk_common.h -- what the two samplers (sample.hip, scene_sample.hip) and the whole-scene chunker (chunker.hip) share: the pad rule, the
 // NaN-propagating min / max, the slice clamp and the base-point bit-row writer.  The rules are pinned in include/mvp_hip.h
-// (mvp_sample_chunks_f32, mvp_scene_chunks_*, mvp_pack_chunks_f32); this is the one place that states them in code.
+// (mvp_sample_chunks_f32, mvp_sample_scenes_f32, mvp_scene_chunks_*, mvp_pack_chunks_f32); this is the one place that states them in
+// code.  The crop half of the resampling rule, which only the samplers need, is keyed_select.h.
 #pragma once
 #include "common.h"   // kWave
 #include "dropout.h"  // lowbias32

@@ -16,57 +16,28 @@
 //   collect_kernel : the nb_pts members with key <= that key as (key, index) pairs, in any order (one returning atomic per wave).
 //   finish_kernel  : one workgroup per chunk: bitonic sort of the pairs in LDS (crop) or the pad rule, then the gather of points and
 //                    labels and the base-point bits.
-// Measurements: DESIGN.md (training chunks).
-#include "chunk_common.h"
+// The keys, the select, the collect and the sort are keyed_select.h's, shared with scene_sample.hip; this file adds what a member is (the
+// box test), the tries and the ordered compaction of pad chunks.  Measurements: DESIGN.md (training chunks).
+#include "keyed_select.h"
 #include <math.h>
 
 namespace {
 
-constexpr int kSmpThreads = 256;
+constexpr int kSmpThreads = kSelThreads;
 constexpr int kSmpMaxSeg = 64;      // workgroups per chunk and pass (one wave scans them in pick_kernel)
 constexpr int kSmpMaxTries = MVP_SAMPLE_MAX_TRIES;
 constexpr int kSmpMaxPts = MVP_SAMPLE_MAX_PTS;  // 8192 (key, index) pairs = 64 KiB of LDS
 constexpr int kFinThreads = 1024;
-constexpr int kBins0 = 256, kBins12 = 4096;
-constexpr int kHistWords = kBins0 + 2 * kBins12;
 
-struct ChunkState {  // per chunk, written by pick_kernel
-  double lo_x, lo_y, hi_x, hi_y;  // the winning box (float32 bounds are exact in double, so later passes compare in double only)
-  int64_t off;                    // first point of the chunk's scene
-  int32_t n;                      // points of the scene
-  int32_t seg;                    // points per workgroup
-  int32_t m;                      // members
-  int32_t all;                    // fallback: every point is a member
-  int32_t crop;                   // m >= nb_pts
-  uint32_t sb;                    // s_b
-  uint32_t prefix;                // radix select: the key bits fixed so far
-  int32_t rank;                   // ... and the rank wanted among the keys sharing them
-  int32_t taken;                  // collect_kernel's counter
-  int32_t pad_;
+struct ChunkState : SelectState {  // per chunk, written by pick_kernel; crop: m >= nb_pts
+  double lo_x, lo_y, hi_x, hi_y;   // the winning box (float32 bounds are exact in double, so later passes compare in double only)
+  int32_t m;                       // members
+  int32_t all;                     // fallback: every point is a member
 };
-
-struct Scene {
-  int64_t off;
-  int32_t n, seg;
-};
-
-// scene of chunk b; indices and offsets are clamped into the arrays, so wrong arguments give wrong results and never a stray access
-__device__ __forceinline__ Scene scene_of(const int64_t* __restrict__ scene_offsets, const int64_t* __restrict__ scene_of_chunk, int b,
-                                          int S, int64_t Ntot, int G) {
-  const int64_t s = clamp_index(scene_of_chunk[b], S);
-  int64_t off = scene_offsets[s], end = scene_offsets[s + 1];
-  clamp_slice(off, end, Ntot);
-  Scene sc;
-  sc.off = off;
-  sc.n = (int32_t)(end - off);
-  const int per = (sc.n + G - 1) / G;
-  sc.seg = (per + kSmpThreads - 1) / kSmpThreads * kSmpThreads;
-  return sc;
-}
 
 // the box of a try in BT = float (ScanNet2D3DChunks) or double (ScanNet3DChunks): (c -/+ half) -/+ margin, each operation rounded once
 template <typename BT>
-__device__ __forceinline__ void try_box(const float* __restrict__ points, const Scene& sc, int64_t ci, BT hx, BT hy, BT mx, BT my, BT& lox,
+__device__ __forceinline__ void try_box(const float* __restrict__ points, const Slice& sc, int64_t ci, BT hx, BT hy, BT mx, BT my, BT& lox,
                                         BT& loy, BT& hix, BT& hiy) {
   if (sc.n <= 0) {
     lox = loy = hix = hiy = (BT)NAN;
@@ -90,11 +61,11 @@ __global__ __launch_bounds__(kSmpThreads) void count_kernel(const float* __restr
   __shared__ int s_m[kSmpThreads / kWave][kSmpMaxTries], s_l[kSmpThreads / kWave][kSmpMaxTries];
   __shared__ float s_ext[kSmpThreads / kWave][4];
   const int g = blockIdx.x, G = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const Scene sc = scene_of(scene_offsets, scene_of_chunk, b, S, Ntot, G);
+  const Slice sc = scene_slice(scene_offsets, scene_of_chunk, b, S, Ntot, G);
   if (tid < T) try_box<BT>(points, sc, center_ind[(size_t)b * T + tid], hx, hy, mx, my, s_lox[tid], s_loy[tid], s_hix[tid], s_hiy[tid]);
   __syncthreads();
-  const int64_t begin = (int64_t)g * sc.seg;
-  const int64_t end = begin + sc.seg < sc.n ? begin + sc.seg : sc.n;
+  int64_t begin, end;
+  segment_range(sc, g, begin, end);
   int mc = 0, lc = 0;
   float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
   for (int64_t base = begin; base < end; base += kSmpThreads) {  // uniform over the workgroup: every lane takes part in the ballots
@@ -183,11 +154,10 @@ struct PickArgs {
 
 __global__ __launch_bounds__(kSmpThreads) void pick_kernel(PickArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
-  uint32_t* hist = a.hist + (size_t)b * kHistWords;
-  for (int i = tid; i < kHistWords; i += kSmpThreads) hist[i] = 0u;
+  zero_hist(a.hist, b);
   if (tid >= kWave) return;
   const int lane = tid, T = a.T, G = a.G;
-  const Scene sc = scene_of(a.scene_offsets, a.scene_of_chunk, b, a.S, a.Ntot, G);
+  const Slice sc = scene_slice(a.scene_offsets, a.scene_of_chunk, b, a.S, a.Ntot, G);
   int m = 0, l = 0;
   if (lane < T)
     for (int g = 0; g < G; ++g) {
@@ -241,21 +211,11 @@ __global__ __launch_bounds__(kSmpThreads) void pick_kernel(PickArgs a) {
   }
   if (lane < G) a.blockoff[(size_t)b * G + lane] = inc - cnt;
   if (lane == 0) {
-    const uint64_t s64 = a.seed_device ? (uint64_t)a.seed_device[0] : a.seed;
-    const uint32_t seed32 = (uint32_t)(s64 ^ (s64 >> 32));
     ChunkState st;
+    select_init(st, sc, mw, a.nb_pts, a.seed_device, a.seed, b);
     st.lo_x = lox, st.lo_y = loy, st.hi_x = hix, st.hi_y = hiy;
-    st.off = sc.off;
-    st.n = sc.n;
-    st.seg = sc.seg;
     st.m = mw;
     st.all = win < 0;
-    st.crop = mw >= a.nb_pts;
-    st.sb = chunk_seed(seed32, b);
-    st.prefix = 0u;
-    st.rank = a.nb_pts;
-    st.taken = 0;
-    st.pad_ = 0;
     a.state[b] = st;
     a.chunk_box[(size_t)b * 4 + 0] = (float)lox;
     a.chunk_box[(size_t)b * 4 + 1] = (float)loy;
@@ -270,6 +230,10 @@ __device__ __forceinline__ bool is_member(const ChunkState& st, float xf, float 
   const double x = xf, y = yf;
   return st.all || (x >= st.lo_x && x <= st.hi_x && y >= st.lo_y && y <= st.hi_y);
 }
+// ... of point j of the chunk's scene
+__device__ __forceinline__ bool is_member(const ChunkState& st, const float* __restrict__ points, int64_t j) {
+  return is_member(st, points[(st.off + j) * 3 + 0], points[(st.off + j) * 3 + 1]);
+}
 
 // PASS 0: compaction (pad chunks) or the histogram of key bits 31..24 (crop chunks); PASS 1 / 2: bits 23..12 / 11..0 of the keys that
 // share the bits fixed so far
@@ -282,20 +246,17 @@ __global__ __launch_bounds__(kSmpThreads) void select_kernel(const float* __rest
   const int g = blockIdx.x, G = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const ChunkState st = state[b];
   if (PASS > 0 && !st.crop) return;
-  const int64_t begin = (int64_t)g * st.seg;
-  const int64_t end = begin + st.seg < st.n ? begin + st.seg : st.n;
+  int64_t begin, end;
+  segment_range(st, g, begin, end);
   if (begin >= end) return;
   uint32_t* hist = hist_all + (size_t)b * kHistWords;
   const bool compact = PASS == 0 && !st.crop;
-  if (PASS == 0 && !compact) {
-    for (int i = tid; i < kBins0; i += kSmpThreads) s_hist[i] = 0u;
-    __syncthreads();
-  }
+  if (!compact) hist_begin<PASS>(s_hist);
   int run = PASS == 0 ? blockoff[(size_t)b * G + g] : 0;
   for (int64_t base = begin; base < end; base += kSmpThreads) {
     const int64_t j = base + tid;
     bool in = false;
-    if (j < end) in = is_member(st, points[(st.off + j) * 3 + 0], points[(st.off + j) * 3 + 1]);
+    if (j < end) in = is_member(st, points, j);
     if (PASS == 0 && compact) {
       const unsigned long long bal = __ballot(in);
       const int before = __popcll(bal & ((1ull << lane) - 1ull));
@@ -312,85 +273,20 @@ __global__ __launch_bounds__(kSmpThreads) void select_kernel(const float* __rest
       run += total;
       __syncthreads();  // s_wtot is rewritten by the next tile
     } else if (in) {
-      const uint32_t key = lowbias32((uint32_t)j ^ st.sb);
-      if (PASS == 0) atomicAdd(&s_hist[key >> 24], 1u);
-      if (PASS == 1 && (key >> 24) == (st.prefix >> 24)) atomicAdd(&hist[kBins0 + ((key >> 12) & 4095u)], 1u);
-      if (PASS == 2 && (key >> 12) == (st.prefix >> 12)) atomicAdd(&hist[kBins0 + kBins12 + (key & 4095u)], 1u);
+      hist_key<PASS>(select_key(j, st.sb), st.prefix, s_hist, hist);
     }
   }
-  if (PASS == 0 && !compact) {
-    __syncthreads();
-    for (int i = tid; i < kBins0; i += kSmpThreads) {
-      const uint32_t v = s_hist[i];
-      if (v) atomicAdd(&hist[i], v);
-    }
-  }
+  if (!compact) hist_end<PASS>(s_hist, hist);
 }
 
-// the digit of pass PASS: the bin d with (keys in bins < d) < rank <= (keys in bins <= d)
 template <int PASS>
 __global__ __launch_bounds__(kSmpThreads) void digit_kernel(ChunkState* __restrict__ state, const uint32_t* __restrict__ hist_all) {
-  constexpr int BINS = PASS == 0 ? kBins0 : kBins12;
-  constexpr int PER = BINS / kSmpThreads;
-  constexpr int SHIFT = PASS == 0 ? 24 : (PASS == 1 ? 12 : 0);
-  __shared__ int s_wtot[kSmpThreads / kWave];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  if (!state[b].crop) return;
-  const int rank = state[b].rank;
-  const uint32_t* hist = hist_all + (size_t)b * kHistWords + (PASS == 0 ? 0 : (PASS == 1 ? kBins0 : kBins0 + kBins12));
-  int v[PER], local = 0;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    v[i] = (int)hist[tid * PER + i];
-    local += v[i];
-  }
-  int inc = local;
-#pragma unroll
-  for (int k = 1; k < kWave; k <<= 1) {
-    const int o = __shfl_up(inc, k, kWave);
-    if (lane >= k) inc += o;
-  }
-  if (lane == kWave - 1) s_wtot[wave] = inc;
-  __syncthreads();  // (also: every thread has read `rank` before the one below rewrites it)
-  int below = inc - local;
-#pragma unroll
-  for (int w = 0; w < kSmpThreads / kWave; ++w) below += w < wave ? s_wtot[w] : 0;
-  if (below < rank && rank <= below + local) {  // exactly one thread: 1 <= rank <= number of keys
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      if (below < rank && rank <= below + v[i]) {
-        state[b].rank = rank - below;
-        state[b].prefix |= (uint32_t)(tid * PER + i) << SHIFT;
-      }
-      below += v[i];
-    }
-  }
+  digit_search<PASS>(state, hist_all);
 }
 
 __global__ __launch_bounds__(kSmpThreads) void collect_kernel(const float* __restrict__ points, ChunkState* __restrict__ state, int nb_pts,
                                                               unsigned long long* __restrict__ pairs) {
-  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
-  const ChunkState st = state[b];
-  if (!st.crop) return;
-  const int64_t begin = (int64_t)g * st.seg;
-  const int64_t end = begin + st.seg < st.n ? begin + st.seg : st.n;
-  for (int64_t base = begin; base < end; base += kSmpThreads) {
-    const int64_t j = base + tid;
-    bool take = false;
-    uint32_t key = 0u;
-    if (j < end && is_member(st, points[(st.off + j) * 3 + 0], points[(st.off + j) * 3 + 1])) {
-      key = lowbias32((uint32_t)j ^ st.sb);
-      take = key <= st.prefix;  // the keys of a chunk are distinct: exactly nb_pts of them
-    }
-    const unsigned long long bal = __ballot(take);
-    if (bal == 0ull) continue;
-    const int leader = __ffsll((long long)bal) - 1;
-    int at = 0;
-    if (lane == leader) at = atomicAdd(&state[b].taken, __popcll(bal));
-    at = __shfl(at, leader, kWave);
-    const int pos = at + __popcll(bal & ((1ull << lane) - 1ull));
-    if (take && pos < nb_pts) pairs[(size_t)b * nb_pts + pos] = ((unsigned long long)key << 32) | (uint32_t)j;
-  }
+  collect_pairs(state, nb_pts, pairs, [points](const ChunkState& st, int64_t j) { return is_member(st, points, j); });
 }
 
 struct FinishArgs {
@@ -414,35 +310,16 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinishArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const ChunkState st = a.state[b];
   const int nb = a.nb_pts, P = a.P;
-  if (st.crop) {
-    for (int i = tid; i < P; i += kFinThreads) buf[i] = i < nb ? a.pairs[(size_t)b * nb + i] : ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < P; i += kFinThreads) {
-          const int o = i ^ j;
-          if (o > i) {
-            const unsigned long long x = buf[i], y = buf[o];
-            if ((x > y) == ((i & k) == 0)) {
-              buf[i] = y;
-              buf[o] = x;
-            }
-          }
-        }
-        __syncthreads();
-      }
-  }
+  if (st.crop) bitonic_sort_lds<kFinThreads>(buf, a.pairs + (size_t)b * nb, nb, P);
   for (int s = tid; s < nb; s += kFinThreads) {
-    int64_t idx;
+    unsigned long long pair = 0ull;
     if (st.crop) {
-      idx = (uint32_t)buf[s];
-    } else if (st.m <= 0) {
-      idx = 0;
-    } else {
-      idx = a.members[(size_t)b * nb + pad_member(s, st.m, st.sb)];
+      pair = buf[s];
+    } else if (st.m > 0) {
+      pair = (uint32_t)a.members[(size_t)b * nb + pad_member(s, st.m, st.sb)];
     }
-    idx = clamp_index(idx, st.n);  // (-1 for a scene without points)
-    a.choice[(size_t)b * nb + s] = idx < 0 ? 0 : idx;
+    const int64_t idx = choice_of(pair, st.n);
+    a.choice[(size_t)b * nb + s] = idx;
     const bool ok = st.n > 0;
     const size_t p = (size_t)(st.off + idx);
 #pragma unroll
@@ -454,20 +331,16 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinishArgs a) {
     write_base_bits<kFinThreads>(a.base_bits + (size_t)b * ((a.nbp + 31) >> 5), a.nbp, [&](int j) {
       if (st.n <= 0) return false;
       const int64_t p = clamp_index(a.base_point_ind[(size_t)sidx * a.nbp + j], st.n);
-      return is_member(st, a.points[(st.off + p) * 3 + 0], a.points[(st.off + p) * 3 + 1]);
+      return is_member(st, a.points, p);
     });
   }
 }
 
-inline int sample_segments(int64_t Ntot) {
-  const int64_t g = cdiv(Ntot, kSmpThreads);
-  return (int)(g < 1 ? 1 : (g > kSmpMaxSeg ? kSmpMaxSeg : g));
-}
+inline int sample_segments(int64_t Ntot) { return segments(Ntot, kSmpThreads, kSmpMaxSeg); }
 
 struct SampleLayout {
   size_t state, hist, pcount, pbox, blockoff, members, pairs, total;
 };
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline SampleLayout sample_layout(int64_t B, int64_t T, int64_t nb_pts, int G) {
   SampleLayout l;
   size_t at = 0;

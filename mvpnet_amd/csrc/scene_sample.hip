@@ -7,162 +7,64 @@
 // The draw is the resampling rule of mvp_sample_chunks_f32 with every point of the scene a member, so no pass reads a coordinate: a
 // point's key is a hash of its index.  A scene is cut into G segments of `seg` consecutive points, one workgroup each:
 //   scene_init_kernel    : per row the scene's slice, s_b, pad or crop; zeroes the row's histograms.
-//   scene_hist_kernel<P> / scene_digit_kernel<P> : radix select of the nb_pts-th smallest key, 8 + 12 + 12 bits (the method of
-//                          sample.hip, private copies: that file's code objects stay as they are).
+//   scene_hist_kernel<P> / scene_digit_kernel<P> : radix select of the nb_pts-th smallest key, 8 + 12 + 12 bits.
 //   scene_collect_kernel : the nb_pts points with key <= that key as (key, index) pairs, in any order (one returning atomic per wave).
 //   scene_tile_kernel    : tiles of 8192 pairs sorted in 64 KiB of LDS (bitonic), in place; a pad row writes its choice here and is done.
 //   scene_merge_kernel   : sorted runs of L pairs merged two by two in global memory, L = 8192, 16384, 32768: a pair's place is its rank
 //                          in its own run + its rank in the sibling run (binary search; the keys are distinct).  Whatever the hash does
 //                          with the keys, the work is the same; the last pass writes `choice`.
-// Pad rows (n < nb_pts) skip the select, the collect, the sort and the merges.  Measurements: DESIGN.md (3D-baseline batches).
-#include "chunk_common.h"
+// Pad rows (n < nb_pts) skip the select, the collect, the sort and the merges.  The state, the keys, the select, the collect and the tile
+// sort are keyed_select.h's, shared with sample.hip; this file adds the merges.  Measurements: DESIGN.md (3D-baseline batches).
+#include "keyed_select.h"
 
 namespace {
 
-constexpr int kScnThreads = 256;
+constexpr int kScnThreads = kSelThreads;
 constexpr int kScnMaxSeg = 256;  // workgroups per row and pass
 constexpr int kScnMaxPts = MVP_SAMPLE_SCENE_MAX_PTS;
 constexpr int kTile = 8192;  // (key, index) pairs sorted in LDS by one workgroup = 64 KiB
 constexpr int kTileThreads = 1024;
-constexpr int kBins0 = 256, kBins12 = 4096;
-constexpr int kHistWords = kBins0 + 2 * kBins12;
 
-struct RowState {  // per row, written by scene_init_kernel
-  int64_t off;      // first point of the row's scene
-  int32_t n;        // points of the scene
-  int32_t seg;      // points per workgroup
-  int32_t crop;     // n >= nb_pts
-  uint32_t sb;      // s_b
-  uint32_t prefix;  // radix select: the key bits fixed so far
-  int32_t rank;     // ... and the rank wanted among the keys sharing them
-  int32_t taken;    // scene_collect_kernel's counter
-  int32_t pad_;
-};
+typedef SelectState RowState;  // per row, written by scene_init_kernel; crop: n >= nb_pts
 
 __global__ __launch_bounds__(kScnThreads) void scene_init_kernel(const int64_t* __restrict__ scene_offsets, const int64_t* __restrict__ scene_of_row,
                                                                  const int64_t* __restrict__ seed_device, uint64_t seed, int S, int64_t Ntot,
                                                                  int G, int nb_pts, RowState* __restrict__ state,
                                                                  uint32_t* __restrict__ hist_all, int32_t* __restrict__ num_points) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  uint32_t* hist = hist_all + (size_t)b * kHistWords;
-  for (int i = tid; i < kHistWords; i += kScnThreads) hist[i] = 0u;
-  if (tid != 0) return;
-  // indices and offsets are clamped into the arrays, so wrong arguments give wrong results and never a stray access
-  const int64_t s = clamp_index(scene_of_row[b], S);
-  int64_t off = scene_offsets[s], end = scene_offsets[s + 1];
-  clamp_slice(off, end, Ntot);
-  const uint64_t s64 = seed_device ? (uint64_t)seed_device[0] : seed;
-  const uint32_t seed32 = (uint32_t)(s64 ^ (s64 >> 32));
+  const int b = blockIdx.x;
+  zero_hist(hist_all, b);
+  if (threadIdx.x != 0) return;
+  const Slice sc = scene_slice(scene_offsets, scene_of_row, b, S, Ntot, G);
   RowState st;
-  st.off = off;
-  st.n = (int32_t)(end - off);
-  const int per = (int)(((int64_t)st.n + G - 1) / G);
-  st.seg = (per + kScnThreads - 1) / kScnThreads * kScnThreads;
-  st.crop = st.n >= nb_pts;
-  st.sb = chunk_seed(seed32, b);
-  st.prefix = 0u;
-  st.rank = nb_pts;
-  st.taken = 0;
-  st.pad_ = 0;
+  select_init(st, sc, sc.n, nb_pts, seed_device, seed, b);
   state[b] = st;
   num_points[b] = st.n;
 }
 
-// histogram of key bits 31..24 (PASS 0), 23..12 / 11..0 of the keys that share the bits fixed so far (PASS 1 / 2)
+// every point of the scene is a member, so no pass reads a coordinate
 template <int PASS>
 __global__ __launch_bounds__(kScnThreads) void scene_hist_kernel(const RowState* __restrict__ state, uint32_t* __restrict__ hist_all) {
   __shared__ uint32_t s_hist[kBins0];
-  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int b = blockIdx.y;
   const RowState st = state[b];
   if (!st.crop) return;
-  const int64_t begin = (int64_t)g * st.seg;
-  const int64_t end = begin + st.seg < st.n ? begin + st.seg : st.n;
+  int64_t begin, end;
+  segment_range(st, blockIdx.x, begin, end);
   if (begin >= end) return;
   uint32_t* hist = hist_all + (size_t)b * kHistWords;
-  if (PASS == 0) {
-    for (int i = tid; i < kBins0; i += kScnThreads) s_hist[i] = 0u;
-    __syncthreads();
-  }
-  for (int64_t j = begin + tid; j < end; j += kScnThreads) {
-    const uint32_t key = lowbias32((uint32_t)j ^ st.sb);
-    if (PASS == 0) atomicAdd(&s_hist[key >> 24], 1u);
-    if (PASS == 1 && (key >> 24) == (st.prefix >> 24)) atomicAdd(&hist[kBins0 + ((key >> 12) & 4095u)], 1u);
-    if (PASS == 2 && (key >> 12) == (st.prefix >> 12)) atomicAdd(&hist[kBins0 + kBins12 + (key & 4095u)], 1u);
-  }
-  if (PASS == 0) {
-    __syncthreads();
-    for (int i = tid; i < kBins0; i += kScnThreads) {
-      const uint32_t v = s_hist[i];
-      if (v) atomicAdd(&hist[i], v);
-    }
-  }
+  hist_begin<PASS>(s_hist);
+  for (int64_t j = begin + threadIdx.x; j < end; j += kScnThreads) hist_key<PASS>(select_key(j, st.sb), st.prefix, s_hist, hist);
+  hist_end<PASS>(s_hist, hist);
 }
 
-// the digit of pass PASS: the bin d with (keys in bins < d) < rank <= (keys in bins <= d)
 template <int PASS>
 __global__ __launch_bounds__(kScnThreads) void scene_digit_kernel(RowState* __restrict__ state, const uint32_t* __restrict__ hist_all) {
-  constexpr int BINS = PASS == 0 ? kBins0 : kBins12;
-  constexpr int PER = BINS / kScnThreads;
-  constexpr int SHIFT = PASS == 0 ? 24 : (PASS == 1 ? 12 : 0);
-  __shared__ int s_wtot[kScnThreads / kWave];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  if (!state[b].crop) return;
-  const int rank = state[b].rank;
-  const uint32_t* hist = hist_all + (size_t)b * kHistWords + (PASS == 0 ? 0 : (PASS == 1 ? kBins0 : kBins0 + kBins12));
-  int v[PER], local = 0;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    v[i] = (int)hist[tid * PER + i];
-    local += v[i];
-  }
-  int inc = local;
-#pragma unroll
-  for (int k = 1; k < kWave; k <<= 1) {
-    const int o = __shfl_up(inc, k, kWave);
-    if (lane >= k) inc += o;
-  }
-  if (lane == kWave - 1) s_wtot[wave] = inc;
-  __syncthreads();  // (also: every thread has read `rank` before the one below rewrites it)
-  int below = inc - local;
-#pragma unroll
-  for (int w = 0; w < kScnThreads / kWave; ++w) below += w < wave ? s_wtot[w] : 0;
-  if (below < rank && rank <= below + local) {  // exactly one thread: 1 <= rank <= number of keys
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      if (below < rank && rank <= below + v[i]) {
-        state[b].rank = rank - below;
-        state[b].prefix |= (uint32_t)(tid * PER + i) << SHIFT;
-      }
-      below += v[i];
-    }
-  }
+  digit_search<PASS>(state, hist_all);
 }
 
 __global__ __launch_bounds__(kScnThreads) void scene_collect_kernel(RowState* __restrict__ state, int nb_pts,
                                                                     unsigned long long* __restrict__ pairs) {
-  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1);
-  const RowState st = state[b];
-  if (!st.crop) return;
-  const int64_t begin = (int64_t)g * st.seg;
-  const int64_t end = begin + st.seg < st.n ? begin + st.seg : st.n;
-  for (int64_t base = begin; base < end; base += kScnThreads) {  // uniform over the wave: every lane takes part in the ballot
-    const int64_t j = base + tid;
-    const uint32_t key = lowbias32((uint32_t)j ^ st.sb);
-    const bool take = j < end && key <= st.prefix;  // the keys of a row are distinct: exactly nb_pts of them
-    const unsigned long long bal = __ballot(take);
-    if (bal == 0ull) continue;
-    const int leader = __ffsll((long long)bal) - 1;
-    int at = 0;
-    if (lane == leader) at = atomicAdd(&state[b].taken, __popcll(bal));
-    at = __shfl(at, leader, kWave);
-    const int pos = at + __popcll(bal & ((1ull << lane) - 1ull));
-    if (take && pos < nb_pts) pairs[(size_t)b * nb_pts + pos] = ((unsigned long long)key << 32) | (uint32_t)j;
-  }
-}
-
-__device__ __forceinline__ int64_t choice_of(unsigned long long pair, int n) {
-  const int64_t idx = clamp_index((int64_t)(uint32_t)pair, n);
-  return idx < 0 ? 0 : idx;
+  collect_pairs(state, nb_pts, pairs, [](const RowState&, int64_t) { return true; });
 }
 
 // tile t of row b: slots [t * kTile, t * kTile + cnt).  Crop rows: the tile's pairs sorted in place (`direct`: nb_pts <= kTile, the one
@@ -183,22 +85,7 @@ __global__ __launch_bounds__(kTileThreads) void scene_tile_kernel(const RowState
   unsigned long long* row = pairs + (size_t)b * nb_pts + lo;
   int P = 1;
   while (P < cnt) P <<= 1;
-  for (int i = tid; i < P; i += kTileThreads) buf[i] = i < cnt ? row[i] : ~0ull;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P; i += kTileThreads) {
-        const int o = i ^ j;
-        if (o > i) {
-          const unsigned long long x = buf[i], y = buf[o];
-          if ((x > y) == ((i & k) == 0)) {
-            buf[i] = y;
-            buf[o] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_lds<kTileThreads>(buf, row, cnt, P);
   for (int i = tid; i < cnt; i += kTileThreads) {
     if (direct) {
       choice[(size_t)b * nb_pts + lo + i] = choice_of(buf[i], st.n);
@@ -240,15 +127,11 @@ __global__ __launch_bounds__(kScnThreads) void scene_merge_kernel(const RowState
   }
 }
 
-inline int scene_segments(int64_t Ntot) {
-  const int64_t g = cdiv(Ntot, 4 * kScnThreads);
-  return (int)(g < 1 ? 1 : (g > kScnMaxSeg ? kScnMaxSeg : g));
-}
+inline int scene_segments(int64_t Ntot) { return segments(Ntot, 4 * kScnThreads, kScnMaxSeg); }
 
 struct SceneLayout {
   size_t state, hist, pairs, pairs2, total;
 };
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline SceneLayout scene_layout(int64_t B, int64_t nb_pts) {
   SceneLayout l;
   size_t at = 0;

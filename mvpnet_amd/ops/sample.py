@@ -11,20 +11,30 @@ MAX_CHUNKS = 65535  # MVP_SAMPLE_MAX_CHUNKS
 _WORKSPACE = {}
 
 
-def _workspace(Ntot, B, T, nb_pts, device):
-    """The call's scratch, one buffer per (size, device).  Safe for calls issued on ONE stream per device (the launches run in stream
-    order); two streams sampling at the same time must call mvp_sample_chunks_f32 with scratch of their own."""
-    nbytes = int(L.lib().mvp_sample_chunks_workspace(Ntot, B, T, nb_pts))
-    ws = _WORKSPACE.get((nbytes, device))
+def _workspace(entry, device, *shape):
+    """The scratch of a call of `entry` (this module's or scene_sample's), one buffer per (entry, size, device): two entry points never
+    share one.  Safe for calls issued on ONE stream per device (the launches run in stream order); two streams sampling at the same time
+    must call the library with scratch of their own."""
+    nbytes = int(getattr(L.lib(), entry + '_workspace')(*shape))
+    ws = _WORKSPACE.get((entry, nbytes, device))
     if ws is None:
-        ws = _WORKSPACE[(nbytes, device)] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        ws = _WORKSPACE[(entry, nbytes, device)] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
     return ws, nbytes
 
 
-def _i64(t, name):
+def _i64(t, name, who='sample_chunks'):
     if not torch.is_tensor(t) or t.dtype != torch.int64:
-        raise RuntimeError('sample_chunks: {} must be an int64 tensor'.format(name))
+        raise RuntimeError('{}: {} must be an int64 tensor'.format(who, name))
     return t
+
+
+def _seed(seed, who):
+    """-> (the 64 bits of an int seed, the device's seed tensor or None)"""
+    if not torch.is_tensor(seed):
+        return int(seed) & (2 ** 64 - 1), None
+    if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
+        raise RuntimeError(who + ': a tensor seed must be one int64 on the device')
+    return 0, seed
 
 
 def sample_chunks(points, seg_label, scene_offsets, scene_of_chunk, center_ind, nb_pts, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2),
@@ -62,11 +72,7 @@ def sample_chunks(points, seg_label, scene_offsets, scene_of_chunk, center_ind, 
         nbp = base_point_ind.size(1)
     sx, sy = (float(v) for v in chunk_size)
     mx, my = (float(v) for v in chunk_margin)
-    seed_dev = None
-    if torch.is_tensor(seed):
-        if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
-            raise RuntimeError('sample_chunks: a tensor seed must be one int64 on the device')
-        seed_dev, seed = seed, 0
+    seed, seed_dev = _seed(seed, 'sample_chunks')
     dev = points.device
     out = {'choice': torch.empty((B, nb_pts), dtype=torch.int64, device=dev),
            'points': torch.empty((B, 3, nb_pts), dtype=torch.float32, device=dev),
@@ -78,9 +84,9 @@ def sample_chunks(points, seg_label, scene_offsets, scene_of_chunk, center_ind, 
         out['base_bits'] = torch.empty((B, (nbp + 31) // 32), dtype=torch.int32, device=dev)
     if B == 0:
         return out
-    ws, nbytes = _workspace(Ntot, B, T, nb_pts, dev)
+    ws, nbytes = _workspace('mvp_sample_chunks', dev, Ntot, B, T, nb_pts)
     L.call('mvp_sample_chunks_f32', points, L.ptr(points), L.ptr(seg_label), L.ptr(scene_offsets), L.ptr(scene_of_chunk), L.ptr(center_ind),
            L.ptr(base_point_ind), Ntot, S, B, T, nbp, nb_pts, sx, sy, mx, my, float(chunk_thresh), int(bool(bounds_f64)),
-           int(seed) & (2 ** 64 - 1), L.ptr(seed_dev), L.ptr(out['choice']), L.ptr(out['points']), L.ptr(out['seg_label']),
+           seed, L.ptr(seed_dev), L.ptr(out['choice']), L.ptr(out['points']), L.ptr(out['seg_label']),
            L.ptr(out['chunk_box']), L.ptr(out['try_index']), L.ptr(out['num_members']), L.ptr(out.get('base_bits')), L.ptr(ws), nbytes)
     return out

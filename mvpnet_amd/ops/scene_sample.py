@@ -4,27 +4,9 @@ mvpnet/data/transforms.py:64-133 behind mvpnet/data/scannet_3d.py:135-221): the 
 import torch
 
 from .. import _lib as L
-from .sample import MAX_CHUNKS
+from .sample import MAX_CHUNKS, _i64, _seed, _workspace
 
 MAX_SCENE_NB_PTS = 65536  # MVP_SAMPLE_SCENE_MAX_PTS: what the sampler's multi-workgroup FPS serves
-
-_WORKSPACE = {}
-
-
-def _workspace(Ntot, B, nb_pts, device):
-    """The call's scratch, one buffer per (size, device).  Safe for calls issued on ONE stream per device (the launches run in stream
-    order); two streams sampling at the same time must call mvp_sample_scenes_f32 with scratch of their own."""
-    nbytes = int(L.lib().mvp_sample_scenes_workspace(Ntot, B, nb_pts))
-    ws = _WORKSPACE.get((nbytes, device))
-    if ws is None:
-        ws = _WORKSPACE[(nbytes, device)] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    return ws, nbytes
-
-
-def _i64(t, name, who):
-    if not torch.is_tensor(t) or t.dtype != torch.int64:
-        raise RuntimeError('{}: {} must be an int64 tensor'.format(who, name))
-    return t
 
 
 def _scenes(scene_offsets, scene_of_row, who):
@@ -47,18 +29,14 @@ def sample_scenes(scene_offsets, scene_of_row, nb_pts, seed=0, Ntot=None):
     Ntot, nb_pts = 2 ** 31 - 1 if Ntot is None else int(Ntot), int(nb_pts)
     if not (1 <= nb_pts <= MAX_SCENE_NB_PTS and B <= MAX_CHUNKS and 1 <= Ntot < 2 ** 31):
         raise RuntimeError('sample_scenes: needs 1 <= nb_pts <= {}, B <= {} and 1 <= Ntot < 2^31'.format(MAX_SCENE_NB_PTS, MAX_CHUNKS))
-    seed_dev = None
-    if torch.is_tensor(seed):
-        if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
-            raise RuntimeError('sample_scenes: a tensor seed must be one int64 on the device')
-        seed_dev, seed = seed, 0
+    seed, seed_dev = _seed(seed, 'sample_scenes')
     dev = scene_offsets.device
     out = {'choice': torch.empty((B, nb_pts), dtype=torch.int64, device=dev), 'num_points': torch.empty((B,), dtype=torch.int32, device=dev)}
     if B == 0:
         return out
-    ws, nbytes = _workspace(Ntot, B, nb_pts, dev)
-    L.call('mvp_sample_scenes_f32', scene_offsets, L.ptr(scene_offsets), L.ptr(scene_of_row), Ntot, S, B, nb_pts, int(seed) & (2 ** 64 - 1),
-           L.ptr(seed_dev), L.ptr(out['choice']), L.ptr(out['num_points']), L.ptr(ws), nbytes)
+    ws, nbytes = _workspace('mvp_sample_scenes', dev, Ntot, B, nb_pts)
+    L.call('mvp_sample_scenes_f32', scene_offsets, L.ptr(scene_offsets), L.ptr(scene_of_row), Ntot, S, B, nb_pts, seed, L.ptr(seed_dev),
+           L.ptr(out['choice']), L.ptr(out['num_points']), L.ptr(ws), nbytes)
     return out
 
 
