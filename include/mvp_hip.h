@@ -651,7 +651,8 @@ int mvp_bn_finalize_f32(const double* stat, int64_t R, int64_t C, float eps, flo
  *   zf (B,N,C1) or NULL, xyz (B,N,3), centre (B,M,3), index (B,M,32) int64 (-1 = empty slot), wxyz (C1,3);
  *   bnL_* = mean, invstd (= 1/sqrt(running_var + eps)), gamma, beta of layer L; W2 (C2,C1), W3 (C3,C2) row-major;
  *   out (B,M,C3), arg (B,M,C3) uint8 or NULL (first neighbour attaining the maximum).
- * MVP_EUNSUPPORTED unless K == 32, C1, C2 <= 64, C3 <= 128, all % 4 == 0 and a split-bf16 precision is set. */
+ * MVP_EUNSUPPORTED unless K == 32, C1, C2 <= 64, C3 <= 128, all % 4 == 0 and a split-bf16 precision is set, and beyond the limits of the
+ * kernel's 32-bit ball and row-offset arithmetic: N, M <= INT_MAX, B * M <= 2^31 - 16, N * max(C1, 3) < 2^32. */
 int mvp_sa_fused_forward_f32(const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz, int64_t B,
                              int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
                              const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,
@@ -944,7 +945,9 @@ int mvp_mlp_weight_grad_ws_f32(const float* dY, const float* X, int64_t R, int64
  * Only dz_2 and dz_1 ever have the shape (B*M*32, C) in memory.  stat: 2*C + 1 float64, ALL zero on entry (sums of y, of y^2, completion
  * counter: zero again on exit); stat_prev: 2*Cp float64 accumulated into.  training = 0 drops the batch terms of the BatchNorm backward.
  * Needs K == 32, C1, C2 <= 64, C3 <= 64 (C3 <= 128 when C1, C2 > 32: level 2 of the reference network), multiples of 4, zf 16-byte aligned, a
- * split-bf16 precision: MVP_EUNSUPPORTED otherwise (callers then take the per-layer entry points). */
+ * split-bf16 precision: MVP_EUNSUPPORTED otherwise (callers then take the per-layer entry points).  mvp_sa_train_forward_f32 and
+ * mvp_sa_train_backward_f32 also return MVP_EUNSUPPORTED beyond the limits of their 32-bit ball and row-offset arithmetic: N, M <= INT_MAX,
+ * B * M <= 2^31 - 16, N * max(C1, 3) < 2^32. */
 int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
                              int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
                              const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,

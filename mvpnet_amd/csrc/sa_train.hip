@@ -25,109 +25,14 @@
 // (reduction over rows) takes as is, and where BatchNorm constants are per-lane.  A wave-private 32 x 36 LDS tile converts between them.
 // Contraction: split-bf16; the forward passes with the forward pieces (bf16x6 by default), the backward passes -- re-computation
 // included, as in the POOL front end of mlp_bwd.hip -- with the backward pieces.
+// The per-ball front end (level input, first-layer tables, gather with the next balls' loads in flight, BatchNorm + ReLU, the tile between
+// the layouts) and the host side of a launch (checks, shape dispatch, grid) are shared with the inference kernel: sa_common.h.
 #include "sa_common.h"
 #include "stats_reduce.h"
 #include <algorithm>
 #include <stdlib.h>
 
 namespace {
-
-struct SaSrc {            // the level's input: what y_1 is re-created from
-  const float* zf;        // (B, N, C1): first-layer feature columns applied per point
-  const float* xyz;       // (B, N, 3)
-  const float* centre;    // (B, M, 3)
-  const int64_t* index;   // (B, M, 32) ball query result (-1 = empty slot: an all-zero row, as in group_lin_rows_kernel)
-  const float* wxyz;      // (C1, 3) first layer's coordinate columns
-  const float* bn1[4];    // BatchNorm 1: mean, invstd, gamma, beta
-  int64_t G;              // B * M balls
-  int N, M, C1;
-};
-
-// first-layer tables of a workgroup: BatchNorm 1 per input channel of layer 2 (k runs along the registers in row layout) and the
-// coordinate columns (wx, wy, wz, 0) per channel
-template <int C1B>
-__device__ __forceinline__ void stage_layer1(const SaSrc& p, float* P1 /* [4][C1B*32] */, float (*Wx)[4], int tid) {
-  for (int k = tid; k < C1B * 32; k += kFT) {
-    const int kc = min(k, p.C1 - 1);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) P1[a * (C1B * 32) + k] = p.bn1[a] ? p.bn1[a][kc] : 0.f;
-    Wx[k][0] = k < p.C1 ? p.wxyz[k * 3 + 0] : 0.f;
-    Wx[k][1] = k < p.C1 ? p.wxyz[k * 3 + 1] : 0.f;
-    Wx[k][2] = k < p.C1 ? p.wxyz[k * 3 + 2] : 0.f;
-    Wx[k][3] = 0.f;
-  }
-}
-
-// y_1 of ball g, row layout: v[sl][tt][e] = zf[j][k] + wxyz[k] . (xyz[j] - centre[g]),  k = 32 sl + 8 tt + 4 lh + e  (same operation
-// order as group_lin_rows_kernel: (wx dx + wy dy) + wz dz, then + zf; an empty slot is a zero row).  In two halves: the loads of the NEXT
-// ball are issued before the current one is worked on (a wave has one or two partners on its SIMD: nothing else hides the gather's
-// round trip through L2 / MALL).
-template <int C1B>
-struct BallRows {
-  float4 z[C1B][4];
-  float p[3], q[3];
-  bool ok;
-};
-// (g: the wave's ball, a SCALAR -- callers pass it through readfirstlane --, so the chunk index, its division and the row bases are scalar
-// arithmetic and the per-lane part of every address is a 32-bit offset: the 64-bit per-lane address arithmetic of the first version was 8 - 10 %
-// of these VALU-bound kernels' vector instructions)
-template <int C1B>
-__device__ __forceinline__ void gather_issue(const SaSrc& p, int g, int64_t j, int lh, BallRows<C1B>& r) {
-  const int b = g / p.M;
-  r.ok = j >= 0 && j < p.N;
-  const unsigned jj = r.ok ? (unsigned)j : 0u;
-  const float* zr = p.zf + (size_t)b * p.N * p.C1 + jj * (unsigned)p.C1;
-#pragma unroll
-  for (int sl = 0; sl < C1B; ++sl)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) r.z[sl][tt] = *reinterpret_cast<const float4*>(zr + min(32 * sl + 8 * tt + 4 * lh, p.C1 - 4));
-  const float* pp = p.xyz + (size_t)b * p.N * 3 + jj * 3u;
-  const float* qc = p.centre + (size_t)g * 3;
-  r.p[0] = pp[0]; r.p[1] = pp[1]; r.p[2] = pp[2];
-  r.q[0] = qc[0]; r.q[1] = qc[1]; r.q[2] = qc[2];
-}
-template <int C1B>
-__device__ __forceinline__ void gather_finish(const BallRows<C1B>& r, int lh, const float (*Wx)[4], float (&v)[C1B][4][4], float (&diff)[3]) {
-  const bool ok = r.ok;
-  const float dx = r.p[0] - r.q[0], dy = r.p[1] - r.q[1], dz = r.p[2] - r.q[2];
-  diff[0] = ok ? dx : 0.f;
-  diff[1] = ok ? dy : 0.f;
-  diff[2] = ok ? dz : 0.f;
-#pragma unroll
-  for (int sl = 0; sl < C1B; ++sl)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int k = 32 * sl + 8 * tt + 4 * lh;
-      const float zz[4] = {r.z[sl][tt].x, r.z[sl][tt].y, r.z[sl][tt].z, r.z[sl][tt].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 w = *reinterpret_cast<const float4*>(&Wx[k + e][0]);
-        float y = (w.x * dx + w.y * dy) + w.z * dz;
-        y = y + zz[e];
-        v[sl][tt][e] = ok ? y : 0.f;
-      }
-    }
-}
-
-// a_1 = relu(bn_1(y_1)) in place, row layout
-template <int C1B>
-__device__ __forceinline__ void act_rows(float (&v)[C1B][4][4], const float* P1, int lh) {
-#pragma unroll
-  for (int sl = 0; sl < C1B; ++sl)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int k = 32 * sl + 8 * tt + 4 * lh;
-      const float4 mm = *reinterpret_cast<const float4*>(P1 + 0 * (C1B * 32) + k), ii = *reinterpret_cast<const float4*>(P1 + 1 * (C1B * 32) + k);
-      const float4 gg = *reinterpret_cast<const float4*>(P1 + 2 * (C1B * 32) + k), bb = *reinterpret_cast<const float4*>(P1 + 3 * (C1B * 32) + k);
-      const float pm[4] = {mm.x, mm.y, mm.z, mm.w}, pi[4] = {ii.x, ii.y, ii.z, ii.w};
-      const float pg[4] = {gg.x, gg.y, gg.z, gg.w}, pb[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a = ((v[sl][tt][e] - pm[e]) * pi[e]) * pg[e] + pb[e];
-        v[sl][tt][e] = a > 0.f ? a : 0.f;
-      }
-    }
-}
 
 // The workgroups of a persistent launch (<= 1024) add their column sums to `stat` themselves; the last one to finish (ticket = the extra
 // element behind the 2 C sums, zero on entry and on exit) finalizes the BatchNorm -- as mlp_stream.hip / stats_reduce_finalize_kernel.
@@ -216,43 +121,17 @@ __global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
   stage_weight<NS>(W2l, p.W2, C2, C1, C2B * 32, C1B, tid);
   if constexpr (STAGE == 3) stage_weight<NS>(W3l, p.W3, C3, C2, C3B * 32, C2B, tid);
   stage_layer1<C1B>(p.s, P1, Wx, tid);
-  float m2[C2B], i2[C2B], g2[C2B], b2[C2B];
-#pragma unroll
-  for (int j = 0; j < C2B; ++j) {
-    m2[j] = i2[j] = g2[j] = b2[j] = 0.f;
-    if constexpr (STAGE == 3) {
-      const int col = min(32 * j + li, C2 - 1);
-      m2[j] = p.bn2[0][col]; i2[j] = p.bn2[1][col]; g2[j] = p.bn2[2][col]; b2[j] = p.bn2[3][col];
-    }
-  }
+  LaneBn<C2B> bn2;
+  if constexpr (STAGE == 3) bn2.load(p.bn2, C2, li);
   float ssum[NBS], qsum[NBS];
 #pragma unroll
   for (int j = 0; j < NBS; ++j) ssum[j] = qsum[j] = 0.f;
   __syncthreads();
   float* st = tiles[wave];
-  const int64_t t_begin = (int64_t)blockIdx.x * p.tiles_per_wg;
-  const int64_t t_end = min(p.s.G, t_begin + p.tiles_per_wg);
-  int g = __builtin_amdgcn_readfirstlane((int)(t_begin + wave));   // (the wave's ball: scalar -- see gather_issue)
-  // pipeline: the index of ball g + 8 and the rows of ball g + 4 are in flight while ball g is worked on
-  BallRows<C1B> rn;
-  int64_t jn = -1;
-  if (PF) {
-    if (g < t_end) gather_issue<C1B>(p.s, g, p.s.index[(size_t)g * 32 + li], lh, rn);
-    if (g + 4 < t_end) jn = p.s.index[(size_t)(g + 4) * 32 + li];
-  } else if (g < t_end) {
-    jn = p.s.index[(size_t)g * 32 + li];  // (without the prefetch only the INDEX of the next ball is in flight)
-  }
-  for (; g < t_end; g += 4) {
-    BallRows<C1B> rc = rn;
-    if (PF && g + 4 < t_end) {
-      gather_issue<C1B>(p.s, g + 4, jn, lh, rn);
-      if (g + 8 < t_end) jn = p.s.index[(size_t)(g + 8) * 32 + li];
-    }
-    if (!PF) {
-      const int64_t j = jn;
-      if (g + 4 < t_end) jn = p.s.index[(size_t)(g + 4) * 32 + li];
-      gather_issue<C1B>(p.s, g, j, lh, rc);
-    }
+  BallPipe<C1B, PF> pipe;
+  for (int g = pipe.begin(p.s, p.tiles_per_wg, wave, li, lh); g < pipe.t_end; g += 4) {
+    BallRows<C1B> rc;
+    pipe.rows(p.s, g, li, lh, rc);
     float v1[C1B][4][4], dif[3];
     gather_finish<C1B>(rc, lh, Wx, v1, dif);
     act_rows<C1B>(v1, P1, lh);
@@ -272,15 +151,13 @@ __global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
         qsum[jb] += q;
       }
     } else {
+      // (act_tile_rows of sa_common.h written out: behind the call the compiler orders the tile's address arithmetic differently, and
+      // sa_train_fwd_kernel<2, 1, 2, 2, 3> then needs 137 + 32 registers instead of 136 + 32 -- one too many for its three waves per SIMD)
       float v2[C2B][4][4];
 #pragma unroll
       for (int jb = 0; jb < C2B; ++jb) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int m = (i & 3) + 8 * (i >> 2) + 4 * lh;
-          const float a = ((acc2[jb][i] - m2[jb]) * i2[jb]) * g2[jb] + b2[jb];
-          st[m * kFLd + li] = a > 0.f ? a : 0.f;
-        }
+        for (int i = 0; i < 16; ++i) st[acc_row(i, lh) * kFLd + li] = bn2.act(jb, acc2[jb][i]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt) {
@@ -299,7 +176,7 @@ __global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
         int rmax = 0, rmin = 0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int m = (i & 3) + 8 * (i >> 2) + 4 * lh;
+          const int m = acc_row(i, lh);
           const float y = acc3[jb][i];
           s += y;
           q += y * y;
@@ -467,35 +344,16 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
   for (int b = 0; b < CPB; ++b) ssum[b] = tsum[b] = txs[b][0] = txs[b][1] = txs[b][2] = 0.f;
   __syncthreads();
 
-  const int64_t t_begin = (int64_t)blockIdx.x * p.tiles_per_wg;
-  const int64_t t_end = min(p.s.G, t_begin + p.tiles_per_wg);
-  int g = __builtin_amdgcn_readfirstlane((int)(t_begin + wave));   // (the wave's ball: scalar -- see gather_issue)
-  // pipeline: the index of ball g + 8 and the rows of ball g + 4 are in flight while ball g is worked on
-  BallRows<C1B> rn;
-  int64_t jn = -1;
-  if (PF) {
-    if (g < t_end) gather_issue<C1B>(p.s, g, p.s.index[(size_t)g * 32 + c], h, rn);
-    if (g + 4 < t_end) jn = p.s.index[(size_t)(g + 4) * 32 + c];
-  } else if (g < t_end) {
-    jn = p.s.index[(size_t)g * 32 + c];
-  }
-  for (; g < t_end; g += 4) {
-    BallRows<C1B> rc = rn;
-    if (PF && g + 4 < t_end) {
-      gather_issue<C1B>(p.s, g + 4, jn, h, rn);
-      if (g + 8 < t_end) jn = p.s.index[(size_t)(g + 8) * 32 + c];
-    }
-    if (!PF) {
-      const int64_t j = jn;
-      if (g + 4 < t_end) jn = p.s.index[(size_t)(g + 4) * 32 + c];
-      gather_issue<C1B>(p.s, g, j, h, rc);
-    }
+  BallPipe<C1B, PF> pipe;
+  for (int g = pipe.begin(p.s, p.tiles_per_wg, wave, c, h); g < pipe.t_end; g += 4) {
+    BallRows<C1B> rc;
+    pipe.rows(p.s, g, c, h, rc);
     float gn[16];
     auto load_g = [&](int a) {  // LAYER 2: channel block a of dz_2 of this ball, accumulator layout (two full 128-byte rows per instruction)
       const float* Gt = p.G + (size_t)g * 32 * C;
       const int col = min(32 * a + c, C - 1);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) gn[q] = Gt[(unsigned)((8 * (q >> 2) + 4 * h + (q & 3)) * C + col)];
+      for (int q = 0; q < 16; ++q) gn[q] = Gt[(unsigned)(acc_row(q, h) * C + col)];
     };
     if constexpr (LAYER == 2) load_g(0);
     // ---- the ball's y_1 (row layout), then x = y_{i-1} in accumulator layout and, for LAYER 2, y_2 in accumulator layout
@@ -514,7 +372,7 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
           *reinterpret_cast<float4*>(tile + c * kFLd + 8 * tt + 4 * h) = make_float4(v1[sl][tt][0], v1[sl][tt][1], v1[sl][tt][2], v1[sl][tt][3]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int q = 0; q < 16; ++q) x[sl][q] = tile[(8 * (q >> 2) + 4 * h + (q & 3)) * kFLd + c];
+        for (int q = 0; q < 16; ++q) x[sl][q] = tile[acc_row(q, h) * kFLd + c];
         __builtin_amdgcn_wave_barrier();
       }
     }
@@ -547,20 +405,10 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
       }
       if constexpr (LAYER == 3) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) tile[(8 * (q >> 2) + 4 * h + (q & 3)) * kFLd + c] = av[q];
+        for (int q = 0; q < 16; ++q) tile[acc_row(q, h) * kFLd + c] = av[q];
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const float4 v0 = *reinterpret_cast<const float4*>(tile + c * kFLd + 16 * s + 4 * h);
-          const float4 v1r = *reinterpret_cast<const float4*>(tile + c * kFLd + 16 * s + 8 + 4 * h);
-          unsigned q0[NS], q1[NS], q2[NS], q3[NS];
-          split_pair<NS>(v0.x, v0.y, q0);
-          split_pair<NS>(v0.z, v0.w, q1);
-          split_pair<NS>(v1r.x, v1r.y, q2);
-          split_pair<NS>(v1r.z, v1r.w, q3);
-#pragma unroll
-          for (int pc = 0; pc < NS; ++pc) far[b][s][pc] = u32x4{q0[pc], q1[pc], q2[pc], q3[pc]};
-        }
+        for (int s = 0; s < 2; ++s) tile_row_frags<NS>(tile, c, h, s, far[b][s]);
         __builtin_amdgcn_wave_barrier();
       }
     }
@@ -599,9 +447,8 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
         const int ar = (int)(p.pool_arg + gb)[go];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int row = 8 * (q >> 2) + 4 * h + (q & 3);
           const float xh = (yl[q] - mu[a]) * is[a];
-          const float d = sc[a] * (((ar == row ? dd : 0.f) - db[a]) - xh * dg[a]);
+          const float d = sc[a] * (((ar == acc_row(q, h) ? dd : 0.f) - db[a]) - xh * dg[a]);
           dyv[q] = cok[a] ? d : 0.f;
         }
       } else {
@@ -631,20 +478,12 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
       }
       // ---- dz_{i-1} += dy[:, block a] . W[block a, :] : the block through the tile -> "8 channels of one row" per lane
 #pragma unroll
-      for (int q = 0; q < 16; ++q) tile[(8 * (q >> 2) + 4 * h + (q & 3)) * kFLd + c] = dyv[q];
+      for (int q = 0; q < 16; ++q) tile[acc_row(q, h) * kFLd + c] = dyv[q];
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const float4 v0 = *reinterpret_cast<const float4*>(tile + c * kFLd + 16 * s + 4 * h);
-        const float4 v1r = *reinterpret_cast<const float4*>(tile + c * kFLd + 16 * s + 8 + 4 * h);
-        unsigned q0[NS], q1[NS], q2[NS], q3[NS];
-        split_pair<NS>(v0.x, v0.y, q0);
-        split_pair<NS>(v0.z, v0.w, q1);
-        split_pair<NS>(v1r.x, v1r.y, q2);
-        split_pair<NS>(v1r.z, v1r.w, q3);
         u32x4 fr[NS];
-#pragma unroll
-        for (int pc = 0; pc < NS; ++pc) fr[pc] = u32x4{q0[pc], q1[pc], q2[pc], q3[pc]};
+        tile_row_frags<NS>(tile, c, h, s, fr);
 #pragma unroll
         for (int b = 0; b < CPB; ++b) {
           const int ci = 32 * b + c;
@@ -672,9 +511,9 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
         d = (xok[b] && xh * pg[b] + pb[b] > 0.f) ? d : 0.f;
         s += d;
         tq += d * xh;
-        tile[(8 * (q >> 2) + 4 * h + (q & 3)) * kFLd + c] = d;
+        tile[acc_row(q, h) * kFLd + c] = d;
         if constexpr (LAYER == 2) {  // (the tile's barriers above ordered the dtile writes before these reads)
-          const float4 dd = *reinterpret_cast<const float4*>(&dtile[wave][8 * (q >> 2) + 4 * h + (q & 3)][0]);
+          const float4 dd = *reinterpret_cast<const float4*>(&dtile[wave][acc_row(q, h)][0]);
           txs[b][0] += d * dd.x;
           txs[b][1] += d * dd.y;
           txs[b][2] += d * dd.z;
@@ -694,21 +533,9 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
     }
   }
 
-  // ---- column sums: lane halves -> waves -> stat_prev (fp64 atomics of <= 1024 workgroups)
-#pragma unroll
-  for (int b = 0; b < CPB; ++b) {
-    const float s = ssum[b] + __shfl_xor(ssum[b], 32, kWave), tq = tsum[b] + __shfl_xor(tsum[b], 32, kWave);
-    if (lane < 32) {
-      sred[0][wave][32 * b + c] = (double)s;
-      sred[1][wave][32 * b + c] = (double)tq;
-    }
-  }
-  __syncthreads();  // also: every wave is done with the images / tiles -> the dW reduction may reuse the LDS
-  for (int col = tid; col < CPB * 32; col += kFT)
-    if (col < Cp) {
-      atomicAdd(p.stat_prev + col, sred[0][0][col] + sred[0][1][col] + sred[0][2][col] + sred[0][3][col]);
-      atomicAdd(p.stat_prev + Cp + col, sred[1][0][col] + sred[1][1][col] + sred[1][2][col] + sred[1][3][col]);
-    }
+  // ---- column sums: lane halves -> waves -> stat_prev (fp64 atomics of <= 1024 workgroups).  Its barrier also says that every wave is done
+  // with the images / tiles: the dW reduction may reuse the LDS.
+  stats_tail<CPB>(ssum, tsum, sred, p.stat_prev, Cp, BnFinalize{}, false);
   if constexpr (LAYER == 2) {
     // dz_1^T . (centred coordinates): lane halves -> waves (through sred, free again behind a barrier) -> ONE fp32 atomic per element and
     // workgroup, spread over 16 slots (one atomic per lane and wave queued 2048 of them on every one of the 3 C1 addresses: +150 us)
@@ -759,7 +586,7 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
         const int ci = 32 * b + c;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int co = 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h;
+          const int co = 32 * a + acc_row(i, h);
           if (co < C && ci < Cp) atomicAdd(p.dW + (size_t)co * p.lddw + ci, accw[a][b][i]);
         }
       }
@@ -1044,21 +871,6 @@ __global__ __launch_bounds__(256) void sa_train_bwd1_kernel(SaBwd1Args p) {
   *reinterpret_cast<float4*>(p.gz + pt * C1 + c) = make_float4(out[0], out[1], out[2], out[3]);
 }
 
-int blocks_of(int64_t c) { return c <= 32 ? 1 : c <= 64 ? 2 : 4; }
-
-bool level_supported(int64_t K, int64_t C1, int64_t C2, int64_t C3) {
-  return K == 32 && C1 >= 4 && C1 <= 64 && C2 <= 64 && C3 <= 128 && C1 % 4 == 0 && C2 % 4 == 0 && C3 % 4 == 0;
-}
-
-// persistent workgroups: as many per CU as LDS -- and `max_per_cu`, what the kernel's registers allow -- let be resident AT ONCE (a launch of
-// 768 workgroups on 512 slots runs two rounds for the work of one and a half)
-int64_t grid_for(int64_t G, int64_t lds_bytes, int64_t* tiles_per_wg, int64_t max_per_cu = 4) {
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(max_per_cu, (150 * 1024) / lds_bytes));
-  const int64_t wgs = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(1024, 256 * per_cu), cdiv(G, 16)));
-  *tiles_per_wg = cdiv(cdiv(G, wgs), 4) * 4;
-  return cdiv(G, *tiles_per_wg);
-}
-
 }  // namespace
 
 // Forward passes 2 / 3 of a set-abstraction level in training mode (see the top of the file).
@@ -1068,7 +880,7 @@ int64_t grid_for(int64_t G, int64_t lds_bytes, int64_t* tiles_per_wg, int64_t ma
 // zf (B,N,C1), xyz (B,N,3), centre (B,M,3), index (B,M,32), wxyz (C1,3), bn1_* = the first layer's finalized BatchNorm.
 // stat: 2*C + 1 float64, ALL zero on entry (C = C2 / C3): column sums of y, of y^2, completion counter (zero again on exit).
 // Needs K == 32, C1, C2 <= 64, C3 <= 64 (or exactly the (<= 64, <= 64, <= 128) block shape with C1, C2 > 32), multiples of 4, a split-bf16
-// precision: MVP_EUNSUPPORTED otherwise.
+// precision, sizes within the limits of sa_level (sa_common.h): MVP_EUNSUPPORTED otherwise.
 MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
                                      int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
                                      const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,
@@ -1076,21 +888,9 @@ MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xy
                                      double* stat, float eps, float momentum, float* mean, float* invstd, float* running_mean,
                                      float* running_var, int64_t* num_batches_tracked, float* ymax, float* ymin, uint8_t* amax,
                                      uint8_t* amin, mvp_stream_t stream) {
-  MVP_NONNULL(zf);
-  MVP_NONNULL(xyz);
-  MVP_NONNULL(centre);
-  MVP_NONNULL(index);
-  MVP_NONNULL(wxyz);
-  MVP_NONNULL(bn1_mean);
-  MVP_NONNULL(bn1_invstd);
-  MVP_NONNULL(bn1_gamma);
-  MVP_NONNULL(bn1_beta);
-  MVP_NONNULL(W2);
   MVP_NONNULL(stat);
   MVP_NONNULL(mean);
   MVP_NONNULL(invstd);
-  MVP_REQUIRE(stage == 2 || stage == 3);
-  MVP_REQUIRE(B >= 0 && N > 0 && M >= 0 && K > 0 && C1 > 0 && C2 > 0);
   if (stage == 3) {
     MVP_NONNULL(bn2_mean);
     MVP_NONNULL(bn2_invstd);
@@ -1101,60 +901,34 @@ MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xy
     MVP_NONNULL(ymin);
     MVP_NONNULL(amax);
     MVP_NONNULL(amin);
-    MVP_REQUIRE(C3 > 0);
   }
+  const bool sizes = stage == 3 ? C3 > 0 : stage == 2;
+  if (stage != 3) C3 = 0;
   const int ns = mlp_fwd_pieces();
-  if (ns == 0 || !level_supported(K, C1, C2, stage == 3 ? C3 : 4) || ((uintptr_t)zf % 16) != 0) return MVP_EUNSUPPORTED;
-  if (B == 0 || M == 0) return MVP_OK;
-  SaFwdArgs a;
-  a.s.zf = zf; a.s.xyz = xyz; a.s.centre = centre; a.s.index = index; a.s.wxyz = wxyz;
-  a.s.bn1[0] = bn1_mean; a.s.bn1[1] = bn1_invstd; a.s.bn1[2] = bn1_gamma; a.s.bn1[3] = bn1_beta;
-  a.s.G = B * M; a.s.N = (int)N; a.s.M = (int)M; a.s.C1 = (int)C1;
-  a.W2 = W2; a.C2 = (int)C2; a.W3 = W3; a.C3 = (int)(stage == 3 ? C3 : 0);
-  a.bn2[0] = bn2_mean; a.bn2[1] = bn2_invstd; a.bn2[2] = bn2_gamma; a.bn2[3] = bn2_beta;
-  a.stat = stat;
-  a.fin = BnFinalize{B * M * K, eps, momentum, mean, invstd, running_mean, running_var, num_batches_tracked};
-  a.ymax = ymax; a.ymin = ymin; a.amax = amax; a.amin = amin;
-  const int c1b = blocks_of(C1), c2b = blocks_of(C2), c3b = stage == 3 ? blocks_of(C3) : 1;
-  const int64_t lds = (int64_t)ns * 2048 * (c1b * c2b + (stage == 3 ? c2b * c3b : 0)) + 32 * 1024;
-  const unsigned grid = (unsigned)grid_for(a.s.G, lds, &a.tiles_per_wg);
+  SaLevel lv;
+  const int rc = sa_level(zf, true, xyz, centre, index, wxyz, B, N, M, K, C1, {bn1_mean, bn1_invstd, bn1_gamma, bn1_beta}, W2, C2, C3,
+                          sizes, ns != 0 && (uintptr_t)zf % 16 == 0, &lv);
+  if (rc != MVP_OK || lv.s.G == 0) return rc;
+  SaFwdArgs a{lv.s, W2, {bn2_mean, bn2_invstd, bn2_gamma, bn2_beta}, W3, (int)C2, (int)C3, stat,
+              BnFinalize{B * M * K, eps, momentum, mean, invstd, running_mean, running_var, num_batches_tracked}, ymax, ymin, amax, amin, 0};
+  const int64_t lds = (int64_t)ns * 2048 * (lv.c1b * lv.c2b + (stage == 3 ? lv.c2b * lv.c3b : 0)) + 32 * 1024;
+  const unsigned grid = sa_grid(lv.s.G, lds, 4, 1024, &a.tiles_per_wg);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define MVP_SAF(A_, B_, C_, ST_)                                                                                     \
-  do {                                                                                                               \
-    if (ns == 1) hipLaunchKernelGGL((sa_train_fwd_kernel<A_, B_, C_, 1, ST_>), dim3(grid), dim3(kFT), 0, s, a);       \
-    else if (ns == 2) hipLaunchKernelGGL((sa_train_fwd_kernel<A_, B_, C_, 2, ST_>), dim3(grid), dim3(kFT), 0, s, a);  \
-    else hipLaunchKernelGGL((sa_train_fwd_kernel<A_, B_, C_, 3, ST_>), dim3(grid), dim3(kFT), 0, s, a);               \
-  } while (0)
-  const int key = c1b * 100 + c2b * 10 + c3b;
-  if (stage == 2) {
-    switch (c1b * 10 + c2b) {
-      case 11: MVP_SAF(1, 1, 1, 2); break;
-      case 12: MVP_SAF(1, 2, 1, 2); break;
-      case 21: MVP_SAF(2, 1, 1, 2); break;
-      case 22: MVP_SAF(2, 2, 1, 2); break;
-      default: return MVP_EUNSUPPORTED;
-    }
-  } else {
-    switch (key) {
-      case 111: MVP_SAF(1, 1, 1, 3); break;
-      case 112: MVP_SAF(1, 1, 2, 3); break;
-      case 121: MVP_SAF(1, 2, 1, 3); break;
-      case 122: MVP_SAF(1, 2, 2, 3); break;
-      case 211: MVP_SAF(2, 1, 1, 3); break;
-      case 212: MVP_SAF(2, 1, 2, 3); break;
-      case 221: MVP_SAF(2, 2, 1, 3); break;
-      case 222: MVP_SAF(2, 2, 2, 3); break;
-      case 224: MVP_SAF(2, 2, 4, 3); break;   // (64, 64, 128): level 2 of the reference network
-      default: return MVP_EUNSUPPORTED;
-    }
-  }
-#undef MVP_SAF
-  return mvp_launch_status();
+  auto launch = [&](auto shapes, auto st) {
+    return sa_pick(shapes, {lv.c1b, lv.c2b, lv.c3b}, [&](auto sh) {
+      sa_pick(SaPieces{}, {ns}, [&](auto pc) {
+        hipLaunchKernelGGL((sa_train_fwd_kernel<decltype(sh)::v[0], decltype(sh)::v[1], decltype(sh)::v[2], decltype(pc)::v[0], decltype(st)::v[0]>),
+                           dim3(grid), dim3(kFT), 0, s, a);
+      });
+    });
+  };
+  const bool found = stage == 3 ? launch(SaShapes3{}, SaRow<3>{}) : launch(SaShapes2{}, SaRow<2>{});
+  return found ? mvp_launch_status() : MVP_EUNSUPPORTED;
 }
 
 // Backward pass of layer 3 (layer == 3) or layer 2 (layer == 2) of the level (see the top of the file).  Level input and bn1 / W2 / bn2
-// (/ W3) as in the forward.  mean_i / invstd_i / gamma_i: BatchNorm of layer `layer`; stat_i (2 C float64): column sums of dz_i and
-// dz_i * xhat_i (layer 3: from mvp_pool_backward_stats_f32; layer 2: what the layer-3 call accumulated into its stat_prev);
+// (/ W3) as in the forward, and the same limits.  mean_i / invstd_i / gamma_i: BatchNorm of layer `layer`; stat_i (2 C float64): column sums
+// of dz_i and dz_i * xhat_i (layer 3: from mvp_pool_backward_stats_f32; layer 2: what the layer-3 call accumulated into its stat_prev);
 // dgamma_i / dbeta_i (C, may be NULL) <- stat_i as float32; training = 0 drops the two batch terms.
 //   layer 3: pool_dout / pool_out / pool_arg (B*M, C3) -> dW (C3, lddw >= C2) +=, dZ (B*M*32, C2) = dz_2, stat_prev (2 C2) +=
 //   layer 2: G = dz_2 (B*M*32, C2)                    -> dW (C2, lddw >= C1) +=, dZ (B*M*32, C1) = dz_1, stat_prev (2 C1) +=,
@@ -1167,16 +941,6 @@ MVP_API int mvp_sa_train_backward_f32(int layer, const float* zf, const float* x
                                       const double* stat_i, float* dgamma_i, float* dbeta_i, int training, const float* G,
                                       const float* pool_dout, const float* pool_out, const uint8_t* pool_arg, float* dW, int64_t lddw,
                                       float* dZ, double* stat_prev, float* tsum, mvp_stream_t stream) {
-  MVP_NONNULL(zf);
-  MVP_NONNULL(xyz);
-  MVP_NONNULL(centre);
-  MVP_NONNULL(index);
-  MVP_NONNULL(wxyz);
-  MVP_NONNULL(bn1_mean);
-  MVP_NONNULL(bn1_invstd);
-  MVP_NONNULL(bn1_gamma);
-  MVP_NONNULL(bn1_beta);
-  MVP_NONNULL(W2);
   MVP_NONNULL(mean_i);
   MVP_NONNULL(invstd_i);
   MVP_NONNULL(gamma_i);
@@ -1184,8 +948,6 @@ MVP_API int mvp_sa_train_backward_f32(int layer, const float* zf, const float* x
   MVP_NONNULL(dW);
   MVP_NONNULL(dZ);
   MVP_NONNULL(stat_prev);
-  MVP_REQUIRE(layer == 2 || layer == 3);
-  MVP_REQUIRE(B >= 0 && N > 0 && M >= 0 && K > 0 && C1 > 0 && C2 > 0 && lddw > 0 && lddw < (1 << 24));
   if (layer == 3) {
     MVP_NONNULL(bn2_mean);
     MVP_NONNULL(bn2_invstd);
@@ -1195,67 +957,40 @@ MVP_API int mvp_sa_train_backward_f32(int layer, const float* zf, const float* x
     MVP_NONNULL(pool_dout);
     MVP_NONNULL(pool_out);
     MVP_NONNULL(pool_arg);
-    MVP_REQUIRE(C3 > 0 && lddw >= C2);
-  } else {
+  } else if (layer == 2) {
     MVP_NONNULL(G);
     MVP_NONNULL(tsum);
-    MVP_REQUIRE(lddw >= C1);
   }
+  const bool sizes = lddw > 0 && lddw < (1 << 24) && (layer == 3 ? C3 > 0 && lddw >= C2 : layer == 2 && lddw >= C1);
+  if (layer != 3) C3 = 0;
   const int ns = mlp_bwd_pieces();
-  if (ns == 0 || !level_supported(K, C1, C2, layer == 3 ? C3 : 4) || ((uintptr_t)zf % 16) != 0 || ((uintptr_t)dZ % 16) != 0) return MVP_EUNSUPPORTED;
-  if (B == 0 || M == 0) return MVP_OK;
-  SaBwdArgs a;
-  a.s.zf = zf; a.s.xyz = xyz; a.s.centre = centre; a.s.index = index; a.s.wxyz = wxyz;
-  a.s.bn1[0] = bn1_mean; a.s.bn1[1] = bn1_invstd; a.s.bn1[2] = bn1_gamma; a.s.bn1[3] = bn1_beta;
-  a.s.G = B * M; a.s.N = (int)N; a.s.M = (int)M; a.s.C1 = (int)C1;
-  a.W2 = W2; a.C2 = (int)C2; a.W3 = W3; a.C3 = (int)(layer == 3 ? C3 : 0);
-  a.bn2[0] = bn2_mean; a.bn2[1] = bn2_invstd; a.bn2[2] = bn2_gamma; a.bn2[3] = bn2_beta;
-  a.mean_i = mean_i; a.invstd_i = invstd_i; a.gamma_i = gamma_i; a.stat_i = stat_i;
-  a.dgamma_i = dbeta_i ? dgamma_i : nullptr; a.dbeta_i = dbeta_i;
-  a.inv_rows = training ? 1.0f / (float)(B * M * K) : 0.f;
-  a.G = G; a.pool_dout = pool_dout; a.pool_out = pool_out; a.pool_arg = pool_arg;
-  a.dW = dW; a.lddw = (int)lddw; a.dZ = dZ; a.stat_prev = stat_prev; a.tsum = tsum;
-  const int c1b = blocks_of(C1), c2b = blocks_of(C2), c3b = layer == 3 ? blocks_of(C3) : 1;
+  SaLevel lv;
+  const int rc = sa_level(zf, true, xyz, centre, index, wxyz, B, N, M, K, C1, {bn1_mean, bn1_invstd, bn1_gamma, bn1_beta}, W2, C2, C3,
+                          sizes, ns != 0 && (uintptr_t)zf % 16 == 0 && (uintptr_t)dZ % 16 == 0, &lv);
+  if (rc != MVP_OK || lv.s.G == 0) return rc;
+  SaBwdArgs a{lv.s, W2, {bn2_mean, bn2_invstd, bn2_gamma, bn2_beta}, W3, (int)C2, (int)C3, mean_i, invstd_i, gamma_i, stat_i,
+              dbeta_i ? dgamma_i : nullptr, dbeta_i, training ? 1.0f / (float)(B * M * K) : 0.f, G, pool_dout, pool_out, pool_arg, dW, (int)lddw, dZ,
+              stat_prev, tsum, 0};
+  const int c1b = lv.c1b, c2b = lv.c2b, c3b = lv.c3b;
   const int cb = layer == 3 ? c3b : c2b, cpb = layer == 3 ? c2b : c1b;
   // y_2 is re-computed with the forward's pieces when those are 3 (the default: forward bf16x6, backward bf16x3), else with the backward's
   const int nsf = (mlp_fwd_pieces() == 3) ? 3 : ns;
   const int64_t lds = (int64_t)2048 * (nsf * c1b * c2b + ns * ((layer == 3 ? c2b * c3b : 0) + cb * cpb)) + 32 * 1024;
   // (registers: two workgroups per CU for the narrow variants -- the kernel's launch bounds --, one for the others)
   const bool narrow = layer == 3 ? c1b * c2b * c3b <= 2 : c1b * c2b == 1;
-  const unsigned grid = (unsigned)grid_for(a.s.G, lds, &a.tiles_per_wg, narrow ? 2 : 1);
+  const unsigned grid = sa_grid(lv.s.G, lds, narrow ? 2 : 1, 1024, &a.tiles_per_wg);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define MVP_SAB(A_, B_, C_, L_)                                                                                          \
-  do {                                                                                                                   \
-    if (ns == 1 && nsf == 3) hipLaunchKernelGGL((sa_train_bwd_kernel<A_, B_, C_, 1, L_, 3>), dim3(grid), dim3(kFT), 0, s, a);      \
-    else if (ns == 1) hipLaunchKernelGGL((sa_train_bwd_kernel<A_, B_, C_, 1, L_, 1>), dim3(grid), dim3(kFT), 0, s, a);             \
-    else if (ns == 2 && nsf == 3) hipLaunchKernelGGL((sa_train_bwd_kernel<A_, B_, C_, 2, L_, 3>), dim3(grid), dim3(kFT), 0, s, a); \
-    else if (ns == 2) hipLaunchKernelGGL((sa_train_bwd_kernel<A_, B_, C_, 2, L_, 2>), dim3(grid), dim3(kFT), 0, s, a);             \
-    else hipLaunchKernelGGL((sa_train_bwd_kernel<A_, B_, C_, 3, L_, 3>), dim3(grid), dim3(kFT), 0, s, a);                          \
-  } while (0)
-  if (layer == 2) {
-    switch (c1b * 10 + c2b) {
-      case 11: MVP_SAB(1, 1, 1, 2); break;
-      case 12: MVP_SAB(1, 2, 1, 2); break;
-      case 21: MVP_SAB(2, 1, 1, 2); break;
-      case 22: MVP_SAB(2, 2, 1, 2); break;
-      default: return MVP_EUNSUPPORTED;
-    }
-  } else {
-    switch (c1b * 100 + c2b * 10 + c3b) {
-      case 111: MVP_SAB(1, 1, 1, 3); break;
-      case 112: MVP_SAB(1, 1, 2, 3); break;
-      case 121: MVP_SAB(1, 2, 1, 3); break;
-      case 122: MVP_SAB(1, 2, 2, 3); break;
-      case 211: MVP_SAB(2, 1, 1, 3); break;
-      case 212: MVP_SAB(2, 1, 2, 3); break;
-      case 221: MVP_SAB(2, 2, 1, 3); break;
-      case 222: MVP_SAB(2, 2, 2, 3); break;
-      case 224: MVP_SAB(2, 2, 4, 3); break;
-      default: return MVP_EUNSUPPORTED;
-    }
-  }
-#undef MVP_SAB
-  return mvp_launch_status();
+  using Pieces = SaTable<SaRow<1, 1>, SaRow<1, 3>, SaRow<2, 2>, SaRow<2, 3>, SaRow<3, 3>>;   // (NS, NSF)
+  auto launch = [&](auto shapes, auto ly) {
+    return sa_pick(shapes, {c1b, c2b, c3b}, [&](auto sh) {
+      sa_pick(Pieces{}, {ns, nsf}, [&](auto pc) {
+        hipLaunchKernelGGL((sa_train_bwd_kernel<decltype(sh)::v[0], decltype(sh)::v[1], decltype(sh)::v[2], decltype(pc)::v[0], decltype(ly)::v[0],
+                                                decltype(pc)::v[1]>), dim3(grid), dim3(kFT), 0, s, a);
+      });
+    });
+  };
+  const bool found = layer == 3 ? launch(SaShapes3{}, SaRow<3>{}) : launch(SaShapes2{}, SaRow<2>{});
+  return found ? mvp_launch_status() : MVP_EUNSUPPORTED;
 }
 
 // Geometry-only sums of a level (see sa_geom_sums_kernel): from the transposed ball index (offsets (B,N+1), slots (B,M*32): mvp_csr_build_i64

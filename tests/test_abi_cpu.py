@@ -54,6 +54,45 @@ def test_argument_errors_do_not_launch():
     assert lib.mvp_pixel_knn_bruteforce_f32(dummy, dummy, dummy, 1, 8, 8, 9, dummy, None, None) == -1
 
 
+def test_set_abstraction_level_limits_are_refused_before_any_launch():
+    """The fused set-abstraction kernels do 32-bit ball and row-offset arithmetic: the three entry points refuse B*M > 2^31 - 16, N or
+    M > INT_MAX and N * max(C1, 3) >= 2^32 with MVP_EUNSUPPORTED, after the null and size checks and before any HIP call (safe without a
+    GPU: every call here is over a limit or invalid)."""
+    import ctypes
+    from mvpnet_amd import _lib
+    lib = _lib.lib()
+    d = ctypes.c_void_p(16)
+    C1, C2, C3 = 64, 64, 128
+    # a split-bf16 precision, set here: without one the entry points answer MVP_EUNSUPPORTED before they look at the limits
+    old = lib.mvp_get_mlp_precision(), lib.mvp_get_mlp_precision_backward()
+    assert lib.mvp_set_mlp_precision(6, _lib._mlp_min_width) == 0 and lib.mvp_set_mlp_precision_backward(3) == 0
+
+    def level(B, N, M, K, xyz):   # zf, xyz, centre, index, wxyz, B, N, M, K, C1, bn1 x 4, W2, C2, bn2 x 4, W3, C3
+        return (d, xyz, d, d, d, B, N, M, K, C1, d, d, d, d, d, C2, d, d, d, d, d, C3)
+
+    def inference(*lv):
+        return lib.mvp_sa_fused_forward_f32(*level(*lv), d, d, d, d, d, None, None)
+
+    def forward(stage):
+        return lambda *lv: lib.mvp_sa_train_forward_f32(stage, *level(*lv), d, 1e-5, 0.1, d, d, None, None, None, d, d, d, d, None)
+
+    def backward(layer):
+        own = (None, d, d, d, None) if layer == 3 else (d, None, None, None, d)   # G, pool_dout, pool_out, pool_arg, tsum
+        return lambda *lv: lib.mvp_sa_train_backward_f32(layer, *level(*lv), d, d, d, d, None, None, 1, *own[:4], d, 64, d, d, own[4], None)
+
+    try:
+        for entry in (inference, forward(2), forward(3), backward(2), backward(3)):
+            assert entry(2 ** 20, 1000, 2 ** 11, 32, d) == -2    # B * M = 2^31
+            assert entry(2, 2 ** 31, 10, 32, d) == -2            # N
+            assert entry(2, 2 ** 26, 10, 32, d) == -2            # N * C1 = 2^32
+            assert entry(2, 1000, 10, 32, None) == -3            # MVP_ENULL comes first, as before
+            assert entry(2, 1000, 10, 0, d) == -1                # ... and so does MVP_EINVAL
+            assert entry(2 ** 20, 1000, 2 ** 11, 32, None) == -3 and entry(2, 2 ** 31, 10, 0, d) == -1
+            assert entry(2, 1000, 10, 0, None) == -3             # a null pointer outranks an invalid size
+    finally:
+        assert lib.mvp_set_mlp_precision(old[0], _lib._mlp_min_width) == 0 and lib.mvp_set_mlp_precision_backward(old[1]) == 0
+
+
 @pytest.mark.parametrize('fn', ['fps', 'ball', 'knn', 'group', 'interp'])
 def test_no_cpu_fallback(fn):
     import mvpnet_amd.ops as ops

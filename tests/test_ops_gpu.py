@@ -1540,6 +1540,45 @@ def test_sa_fused_inference_kernel(dev, cin, widths, N, M):
     np.testing.assert_allclose(res[3].cpu().numpy(), res[2].cpu().numpy(), rtol=1e-5, atol=1e-5)
 
 
+@pytest.mark.parametrize('with_zf', [True, False])
+def test_sa_fused_inference_kernel_arg_output(dev, with_zf):
+    """The `arg` output of mvp_sa_fused_forward_f32 (the row of the ball that attains the pooled maximum), through the C ABI on a hand-built
+    index: asking for it does not change `out`; a ball whose 32 slots hold ONE neighbour ties exactly in every column and the lowest row
+    (0) wins, across the lane halves too; and permuting the slots of a ball of distinct neighbours (some slots empty) leaves `out` bit-equal
+    and `arg` pointing at the same neighbour wherever out > 0 (columns pooled to 0 tie at ReLU's zero: the first row wins there)."""
+    from mvpnet_amd import _lib as L
+    B, N, M, K, C1, C2, C3 = 2, 64, 10, 32, 16, 32, 32
+    gen = torch.Generator().manual_seed(11 + with_zf)
+    rnd = lambda *s: torch.randn(*s, generator=gen).to(dev)
+    index, perm = torch.empty(B, M, K, dtype=torch.int64), torch.empty(B, M, K, dtype=torch.int64)
+    for b in range(B):
+        for m in range(M):   # (M is even: ball b * M + m is even when m is)
+            if m % 2 == 0:
+                index[b, m], perm[b, m] = (7 * (b * M + m) + 3) % N, torch.arange(K)
+            else:
+                index[b, m], perm[b, m] = torch.randperm(N, generator=gen)[:K], torch.randperm(K, generator=gen)
+                index[b, m, [3, 17, 30]] = -1
+    index2 = torch.gather(index, 2, perm)
+    xyz, centre, zf = rnd(B, N, 3), rnd(B, M, 3), rnd(B, N, C1) if with_zf else None
+    wxyz, W2, W3 = rnd(C1, 3), rnd(C2, C1) / 4, rnd(C3, C2) / 4
+    bn = [t for C in (C1, C2, C3) for t in (0.2 * rnd(C), 0.5 + torch.rand(C, generator=gen).to(dev), rnd(C), 0.2 * rnd(C))]   # gamma of either sign
+
+    def run(idx, want_arg):
+        idx = idx.to(dev)
+        out = torch.full((B, M, C3), float('nan'), device=dev)
+        arg = torch.full((B, M, C3), 255, dtype=torch.uint8, device=dev) if want_arg else None
+        L.call('mvp_sa_fused_forward_f32', xyz, L.ptr(zf), L.ptr(xyz), L.ptr(centre), L.ptr(idx), L.ptr(wxyz), B, N, M, K, C1, *map(L.ptr, bn[0:4]),
+               L.ptr(W2), C2, *map(L.ptr, bn[4:8]), L.ptr(W3), C3, *map(L.ptr, bn[8:12]), L.ptr(out), L.ptr(arg))
+        return out.cpu(), None if arg is None else arg.cpu().long()
+
+    (out0, _), (out1, arg1), (out2, arg2) = run(index, False), run(index, True), run(index2, True)
+    assert torch.equal(out0, out1) and torch.equal(out2, out1) and not torch.isnan(out1).any()
+    assert (arg1[:, 0::2] == 0).all() and int(arg1.max()) < K
+    pos = out1 > 0
+    assert pos[:, 1::2].any() and len(torch.unique((arg1[:, 1::2][pos[:, 1::2]] >> 2) & 1)) == 2   # maxima in both lane halves
+    assert torch.equal(torch.gather(index, 2, arg1)[pos], torch.gather(index2, 2, arg2)[pos])
+
+
 @pytest.mark.parametrize('kind', ['uniform', 'clusters', 'lattice', 'duplicates', 'coincident', 'plane'])
 @pytest.mark.parametrize('N,M', [(8192, 2048), (5000, 1300), (4096, 4096), (3000, 700)])
 def test_fps_exact_on_structured_clouds(dev, kind, N, M):
