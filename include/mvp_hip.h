@@ -561,7 +561,7 @@ int mvp_group_lin_rows_bn_f32(const float* zf, const float* xyz, const float* ce
 /* stat (2*C float64) += column sums of y and y^2 over the R rows of y (R,C); accumulated: the caller provides zeros */
 int mvp_colstats_f32(const float* y, int64_t R, int64_t C, double* stat, double* partial, mvp_stream_t stream);
 /* `partial` of mvp_colstats_f32 / mvp_bn_rows_forward_f32 / mvp_bn_rows_backward_f32: optional scratch of
- * mvp_colstats_partial_count(G*K rows, C) float64.  With it the column sums are reduced through per-workgroup slots by up to 2048
+ * mvp_colstats_partial_count(G*K rows, C) float64.  With it the column sums are reduced through per-workgroup slots by up to 1024
  * workgroups; without it (NULL) by at most 256 workgroups with fp64 atomics, which queue per result address. */
 int64_t mvp_colstats_partial_count(int64_t R, int64_t C);
 int mvp_interp_rows_f32(const float* feature, const int64_t* index, const float* weight, int64_t B, int64_t N1, int64_t C,

@@ -739,9 +739,11 @@ struct BwdSum {  // rows r = g*K + k; every row of group g receives dout[g] (gra
 };
 
 // Persistent, grid-stride: a few hundred workgroups walk the rows with 4 independent 16-byte loads in flight per lane,
-// sum runs of <= 64 rows in fp32 and carry the run totals in fp64 registers.  The number of workgroups is the number of
-// fp64 atomics that queue on each of the 2*C result addresses (~90 ns each, measured: with 2048 workgroups that queue
-// alone cost 180 us per call whatever the tensor size), so it is kept small and scales with the tensor.
+// sum runs of <= 64 rows in fp32 and carry the run totals in fp64 registers.  Without scratch slots the number of workgroups is
+// the number of fp64 atomics that queue on each of the 2*C result addresses (~90 ns each, measured: with 2048 workgroups that queue
+// alone cost 180 us per call whatever the tensor size), so it is kept small and scales with the tensor; with slots
+// (colstats_blocks_partial) the count follows the tensor and the CUs instead.  Eight loads in flight per lane were measured slower
+// (BwdSum 80 -> 96 us).
 template <typename Src>
 __global__ __launch_bounds__(kRT) void colstats_kernel(Src src, int64_t R, int C, double* __restrict__ stat,
                                                        double* __restrict__ partial, int zero_stat) {
@@ -1042,9 +1044,13 @@ int check_rows(int64_t R, int64_t C) {
   return MVP_OK;
 }
 
-// Workgroups of the scratch-buffer variant: one per ~32 KB of rows (a handful of 4-deep load rounds per lane), 16 .. 2048.
+// Workgroups of the scratch-buffer variant: one per ~16 KB of rows, 16 .. 1024.  Measured in the B = 32 step
+// (profiles/small_reductions.txt): the 7 MB passes (BwdMax) want the many short workgroups (10.2 -> 7.6 us with 448 instead of 224),
+// the 786 432 x 64 pass (BwdSum) wants every workgroup resident at once with an equal share -- 1024 = four per CU: 52 us, against 80 us
+// with 2048 and 73 - 75 us with 4096 - 6144.  The slots are summed by stats_reduce_kernel, whose time does not move with their number
+// in this range.
 inline int64_t colstats_blocks_partial(int64_t R, int64_t C) {
-  return std::min<int64_t>(2048, std::max<int64_t>(16, cdiv(R * C * 4, 32 * 1024)));
+  return std::min<int64_t>(1024, std::max<int64_t>(16, cdiv(R * C * 4, 16 * 1024)));
 }
 
 // zero_stat: `stat` is (re)initialised by this call (the BatchNorm passes) instead of accumulated into (mvp_colstats_f32)

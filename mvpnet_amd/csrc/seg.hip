@@ -62,6 +62,122 @@ __device__ __forceinline__ float row_lse(const float* __restrict__ p, int64_t ld
   return logf(se);
 }
 
+// ---- channels-last rows, C % 4 == 0, C <= kRegC, contiguous and 16-byte aligned: the wave-coalesced path -------------------------
+// A wave's 64 rows are 64 * C contiguous floats.  With one row per lane straight from memory the lanes of a load sit 4 C bytes apart
+// (every 16-byte load of the wave touches 64 different places).  Here lane l loads quads l, l + 64, ... of the wave's block -- C / 4
+// fully coalesced 16-byte loads, nothing past C -- and the wave's slice of LDS hands each lane its own row (and takes the gradient
+// rows back the same way).  Same values into the same arithmetic as row_lse: results do not change.
+constexpr int kRegQ = kRegC / 4;
+typedef float4 SegTile[kWave * kRegQ];  // one wave's 64 rows of up to kRegC floats (8 KB)
+
+__device__ __forceinline__ bool seg_rows_layout(const float* p, int64_t B, int C, int64_t N, int64_t ld_b, int64_t ld_c, int64_t ld_n) {
+  return ld_c == 1 && ld_n == C && (B == 1 || ld_b == N * C) && (C & 3) == 0 && C <= kRegC && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+
+// x[0 .. 4 Q) = logits of row (row0 + lane), row0 = first row of this wave's 64; rows >= R read as zeros.  Block-uniform call.
+template <int Q>
+__device__ __forceinline__ void seg_load_rows(const float* __restrict__ logit, int64_t row0, int64_t R, float4* tile, float* x) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t q0 = row0 * Q, nq = R * Q;
+  float4 v[Q];
+#pragma unroll
+  for (int i = 0; i < Q; ++i) {
+    const int64_t k = q0 + lane + i * kWave;
+    v[i] = k < nq ? *reinterpret_cast<const float4*>(logit + 4 * k) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  __syncthreads();  // the tile's previous readers are done
+#pragma unroll
+  for (int i = 0; i < Q; ++i) tile[lane + i * kWave] = v[i];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const float4 t = tile[lane * Q + q];
+    x[4 * q + 0] = t.x; x[4 * q + 1] = t.y; x[4 * q + 2] = t.z; x[4 * q + 3] = t.w;
+  }
+}
+
+// row_lse on registers: same max (row_lse's entries >= C repeat the last class), same sum order
+template <int Q>
+__device__ __forceinline__ float regs_lse(const float* x, float* mx_out) {
+  float mx = x[0], se = 0.f;
+#pragma unroll
+  for (int c = 1; c < 4 * Q; ++c) mx = fmaxf(mx, x[c]);
+#pragma unroll
+  for (int c = 0; c < 4 * Q; ++c) se += expf(x[c] - mx);
+  *mx_out = mx;
+  return logf(se);
+}
+
+// One workgroup's share of the forward sums on this layout: the same rows per lane, in the same order, as the strided loop.
+template <int Q>
+__device__ __forceinline__ void seg_loss_rows(const float* __restrict__ logit, int64_t R, const int64_t* __restrict__ label,
+                                              const float* __restrict__ weight, int64_t ignore_index, float4* tile, double& s_nll,
+                                              double& s_w) {
+  constexpr int C = 4 * Q;
+  for (int64_t base = (int64_t)blockIdx.x * kST; base < R; base += (int64_t)gridDim.x * kST) {
+    const int64_t r = base + threadIdx.x;
+    const int64_t y = r < R ? label[r] : -1;
+    float x[C], mx;
+    seg_load_rows<Q>(logit, base + (threadIdx.x & ~(kWave - 1)), R, tile, x);
+    if (r >= R || y == ignore_index || y < 0 || y >= C) continue;
+    const float lse = regs_lse<Q>(x, &mx);
+    float xy = x[0];  // x[y] from the registers: a compare-select chain, not a second global load that waits for the label
+#pragma unroll
+    for (int c = 1; c < C; ++c) xy = c == (int)y ? x[c] : xy;
+    const float nll = (mx + lse) - xy;
+    const float w = weight ? weight[y] : 1.f;
+    s_nll += (double)(w * nll);
+    s_w += (double)w;
+  }
+}
+
+// One workgroup's 256 gradient rows on this layout (logits and gradient both).
+template <int Q>
+__device__ __forceinline__ void seg_loss_bwd_rows(const float* __restrict__ logit, int64_t R, const int64_t* __restrict__ label,
+                                                  const float* __restrict__ weight, int64_t ignore_index, const double* __restrict__ acc,
+                                                  const float* __restrict__ grad_out, float* __restrict__ grad, float4* tile) {
+  constexpr int C = 4 * Q;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t row0 = (int64_t)blockIdx.x * kST + (threadIdx.x & ~(kWave - 1)), r = row0 + lane;
+  const int64_t y = r < R ? label[r] : -1;
+  const bool valid = r < R && y != ignore_index && y >= 0 && y < C;
+  float x[C], mx;
+  seg_load_rows<Q>(logit, row0, R, tile, x);
+  const float lse = regs_lse<Q>(x, &mx);
+  const float scale = valid ? (float)((double)(*grad_out) * (double)(weight ? weight[y] : 1.f) / acc[1]) : 0.f;
+  __syncthreads();  // every lane has its row: the tile takes the gradient rows
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    float gv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 4 * q + i;
+      gv[i] = valid ? scale * (expf((x[c] - mx) - lse) - (c == (int)y ? 1.f : 0.f)) : 0.f;  // exact zeros for ignored points
+    }
+    tile[lane * Q + q] = make_float4(gv[0], gv[1], gv[2], gv[3]);
+  }
+  __syncthreads();
+  const int64_t q0 = row0 * Q, nq = R * Q;
+#pragma unroll
+  for (int i = 0; i < Q; ++i) {
+    const int64_t k = q0 + lane + i * kWave;
+    if (k < nq) *reinterpret_cast<float4*>(grad + 4 * k) = tile[lane + i * kWave];
+  }
+}
+
+// the eight widths of the layout (C = 4 .. 32): exact trip counts, no guard per class
+#define SEG_ROWS_DISPATCH(C, CALL)  \
+  switch ((C) >> 2) {               \
+    case 1: CALL(1); break;         \
+    case 2: CALL(2); break;         \
+    case 3: CALL(3); break;         \
+    case 4: CALL(4); break;         \
+    case 5: CALL(5); break;         \
+    case 6: CALL(6); break;         \
+    case 7: CALL(7); break;         \
+    default: CALL(8); break;        \
+  }
+
 // acc[0] += sum w[y] * nll, acc[1] += sum w[y] over the valid points; the LAST workgroup (ticket in acc[2], as an
 // unsigned 64-bit counter) writes loss = acc[0] / acc[1] -- no separate division launch.
 __global__ __launch_bounds__(kST) void seg_loss_kernel(const float* __restrict__ logit, int64_t B, int C, int64_t N, int64_t ld_b,
@@ -69,8 +185,14 @@ __global__ __launch_bounds__(kST) void seg_loss_kernel(const float* __restrict__
                                                        const float* __restrict__ weight, int64_t ignore_index,
                                                        double* __restrict__ acc, float* __restrict__ loss) {
   __shared__ double red[kST / kWave];
+  __shared__ SegTile tile[kST / kWave];
   const int64_t R = B * N;
   double s_nll = 0.0, s_w = 0.0;
+  if (seg_rows_layout(logit, B, C, N, ld_b, ld_c, ld_n)) {
+#define SEG_CALL(Q) seg_loss_rows<Q>(logit, R, label, weight, ignore_index, tile[threadIdx.x >> 6], s_nll, s_w)
+    SEG_ROWS_DISPATCH(C, SEG_CALL)
+#undef SEG_CALL
+  } else  // any other layout: one row per lane at its strides
   for (int64_t r = (int64_t)blockIdx.x * kST + threadIdx.x; r < R; r += (int64_t)gridDim.x * kST) {
     const int64_t y = label[r];
     if (y == ignore_index || y < 0 || y >= C) continue;
@@ -105,8 +227,15 @@ __global__ __launch_bounds__(kST) void seg_loss_bwd_kernel(const float* __restri
                                                            const float* __restrict__ weight, int64_t ignore_index,
                                                            const double* __restrict__ acc, const float* __restrict__ grad_out,
                                                            float* __restrict__ grad, int64_t gld_b, int64_t gld_c, int64_t gld_n) {
+  __shared__ SegTile tile[kST / kWave];
   const int64_t R = B * N;
   const int64_t r = (int64_t)blockIdx.x * kST + threadIdx.x;
+  if (seg_rows_layout(logit, B, C, N, ld_b, ld_c, ld_n) && seg_rows_layout(grad, B, C, N, gld_b, gld_c, gld_n)) {
+#define SEG_CALL(Q) seg_loss_bwd_rows<Q>(logit, R, label, weight, ignore_index, acc, grad_out, grad, tile[threadIdx.x >> 6])
+    SEG_ROWS_DISPATCH(C, SEG_CALL)
+#undef SEG_CALL
+    return;
+  }
   if (r >= R) return;
   const int64_t b = r / N, n = r - b * N;
   float* g = grad + b * gld_b + n * gld_n;
