@@ -942,7 +942,7 @@ int mvp_mlp_weight_grad_ws_f32(const float* dY, const float* X, int64_t R, int64
  *             mvp_sa_train_backward1_f32: per POINT: a plain gather of dz_1 through the transposed ball index (mvp_csr_build_i64) + the
  *                     closed-form BatchNorm-backward terms -> gradient of zf; gradient of the first layer's coordinate columns from tsum
  *                     (accumulated by the layer-2 pass), zsum, gsum; dgamma1 / dbeta1
- * Only dz_2 and dz_1 ever have the shape (B*M*32, C) in memory.  stat: 2*C + 1 float64, ALL zero on entry (sums of y, of y^2, completion
+ * Only dz_2 and dz_1 ever have the shape (B*M*32, C) in memory -- and y_2, where the caller chooses the _y2 forms below.  stat: 2*C + 1 float64, ALL zero on entry (sums of y, of y^2, completion
  * counter: zero again on exit); stat_prev: 2*Cp float64 accumulated into.  training = 0 drops the batch terms of the BatchNorm backward.
  * Needs K == 32, C1, C2 <= 64, C3 <= 64 (C3 <= 128 when C1, C2 > 32: level 2 of the reference network), multiples of 4, zf 16-byte aligned, a
  * split-bf16 precision: MVP_EUNSUPPORTED otherwise (callers then take the per-layer entry points).  mvp_sa_train_forward_f32 and
@@ -962,6 +962,27 @@ int mvp_sa_train_backward_f32(int layer, const float* zf, const float* xyz, cons
                               const float* mean_i, const float* invstd_i, const float* gamma_i, const double* stat_i, float* dgamma_i,
                               float* dbeta_i, int training, const float* G, const float* pool_dout, const float* pool_out,
                               const uint8_t* pool_arg, float* dW, int64_t lddw, float* dZ, double* stat_prev, float* tsum, mvp_stream_t stream);
+/* The same two with y_2 STORED once instead of re-created by every pass that needs it: one more parameter in front of the stream,
+ * Y2 (B*M*32, C2) float32, 16-byte aligned.  forward(stage 2) also writes y_2 there; forward(stage 3), backward(layer 3) and backward(layer 2)
+ * read it and skip the chain that re-creates it (the level's rows -> BatchNorm 1 + ReLU -> the contraction with W2).  Every pass may be
+ * given Y2 or not independently of the others (the values are the same bit for bit: stage 3 repeats stage 2's code and the backward
+ * re-computes with the forward's split), as long as the stage-2 call that precedes a reader was given it.  Y2 == NULL: exactly
+ * mvp_sa_train_forward_f32 / mvp_sa_train_backward_f32.  MVP_EUNSUPPORTED for a Y2 that is not 16-byte aligned. */
+int mvp_sa_train_forward_y2_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
+                                int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
+                                const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,
+                                const float* bn2_invstd, const float* bn2_gamma, const float* bn2_beta, const float* W3, int64_t C3,
+                                double* stat, float eps, float momentum, float* mean, float* invstd, float* running_mean,
+                                float* running_var, int64_t* num_batches_tracked, float* ymax, float* ymin, uint8_t* amax, uint8_t* amin,
+                                float* Y2, mvp_stream_t stream);
+int mvp_sa_train_backward_y2_f32(int layer, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
+                                 int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
+                                 const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,
+                                 const float* bn2_invstd, const float* bn2_gamma, const float* bn2_beta, const float* W3, int64_t C3,
+                                 const float* mean_i, const float* invstd_i, const float* gamma_i, const double* stat_i, float* dgamma_i,
+                                 float* dbeta_i, int training, const float* G, const float* pool_dout, const float* pool_out,
+                                 const uint8_t* pool_arg, float* dW, int64_t lddw, float* dZ, double* stat_prev, float* tsum, const float* Y2,
+                                 mvp_stream_t stream);
 int mvp_sa_train_backward1_f32(const float* dz1, const int32_t* offsets, const int32_t* slots, const float* zf, const float* dsum,
                                const float* wxyz, const float* tsum, const double* zsum, const double* gsum, int64_t B, int64_t N, int64_t M,
                                int64_t K, int64_t C1, const float* mean, const float* invstd, const float* gamma, const double* stat,
@@ -1042,6 +1063,19 @@ int mvp_sa_train_backward_p_f32(int layer, const float* zf, const float* xyz, co
     float* gamma_i, const double* stat_i, float* dgamma_i, float* dbeta_i, int training, const float* G, const float* pool_dout,
     const float* pool_out, const uint8_t* pool_arg, float* dW, int64_t lddw, float* dZ, double* stat_prev, float* tsum, int precision, int
     precision_backward, mvp_stream_t stream);
+int mvp_sa_train_forward_y2_p_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const
+    float* wxyz, int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd, const
+    float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean, const float* bn2_invstd, const
+    float* bn2_gamma, const float* bn2_beta, const float* W3, int64_t C3, double* stat, float eps, float momentum, float* mean,
+    float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* ymax, float* ymin, uint8_t*
+    amax, uint8_t* amin, float* Y2, int precision, int precision_backward, mvp_stream_t stream);
+int mvp_sa_train_backward_y2_p_f32(int layer, const float* zf, const float* xyz, const float* centre, const int64_t* index, const
+    float* wxyz, int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd, const
+    float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean, const float* bn2_invstd, const
+    float* bn2_gamma, const float* bn2_beta, const float* W3, int64_t C3, const float* mean_i, const float* invstd_i, const
+    float* gamma_i, const double* stat_i, float* dgamma_i, float* dbeta_i, int training, const float* G, const float* pool_dout,
+    const float* pool_out, const uint8_t* pool_arg, float* dW, int64_t lddw, float* dZ, double* stat_prev, float* tsum, const float* Y2,
+    int precision, int precision_backward, mvp_stream_t stream);
 
 /* ---- the coordinate-only work of a PointNet++ (SSG) network in ONE call (csrc/plan.hip) -----------------------------------------------
  * replaces the geometry half of SetAbstraction / FeatureInterpolator called level after level from Python (mvpnet/models/pn2/modules.py:

@@ -118,6 +118,11 @@ _SIGNATURES = {
     'mvp_sa_train_backward_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
                                   _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
                                   _ptr, _ptr],
+    'mvp_sa_train_forward_y2_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
+                                    _ptr, _ptr, _ptr, _i64, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    'mvp_sa_train_backward_y2_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
+                                     _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
+                                     _ptr, _ptr, _ptr],
     'mvp_sa_train_backward1_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr,
                                    ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
     'mvp_pn2_plan_f32': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, ctypes.c_int, _f32, _ptr, _i64, _ptr, _ptr, _ptr],
@@ -155,7 +160,8 @@ _SIGNATURES = {
 # the shared-MLP entry points with the precision as arguments (csrc/mlp_prec.hip): base parameters + (precision, precision_backward)
 for _n in ['mvp_mlp_forward_f32', 'mvp_mlp_forward_bn_f32', 'mvp_mlp_forward_rel_bn_f32', 'mvp_mlp_forward_pool_f32', 'mvp_mlp_input_grad_f32', 'mvp_mlp_input_grad_dropout_f32',
            'mvp_mlp_weight_grad_f32', 'mvp_mlp_weight_grad_ws_f32', 'mvp_mlp_layer_backward_f32', 'mvp_mlp_layer_backward_ws_f32',
-           'mvp_sa_fused_forward_f32', 'mvp_sa_train_forward_f32', 'mvp_sa_train_backward_f32']:
+           'mvp_sa_fused_forward_f32', 'mvp_sa_train_forward_f32', 'mvp_sa_train_backward_f32', 'mvp_sa_train_forward_y2_f32',
+           'mvp_sa_train_backward_y2_f32']:
     _SIGNATURES[_n[:-4] + '_p_f32'] = _SIGNATURES[_n][:-1] + [ctypes.c_int, ctypes.c_int, _ptr]
 # (precision as arguments from the start: there is no process-default twin of this one)
 _SIGNATURES['mvp_mlp_layer_backward_wide_p_f32'] = [_ptr] * 9 + [ctypes.c_int, ctypes.c_int, _f32, ctypes.c_uint64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
@@ -448,10 +454,14 @@ def call_on(stream, name, *args, prec=None):
         check(code, name)
 
 
-def call(name, tensor_for_device, *args, prec=None):
+def call(name, tensor_for_device, *args, prec=None, y2=None):
     """Invoke `name(*args, stream)` on the current stream of tensor_for_device's device.
-    prec = (precision, precision_backward): the `_p_f32` variant of a shared-MLP entry point, precision as arguments."""
+    prec = (precision, precision_backward): the `_p_f32` variant of a shared-MLP entry point, precision as arguments.
+    y2 = device address of the stored y_2: the `_y2_f32` variant of mvp_sa_train_forward_f32 / mvp_sa_train_backward_f32, the address as one
+    more argument."""
     index = tensor_for_device.device.index
+    if y2 is not None:
+        name, args = name[:-4] + '_y2_f32', args + (y2,)
     if DW_WORKSPACE and name in _DW_WS_NAMES:
         handle = _raw_stream(index) if _raw_stream is not None else torch.cuda.current_stream(tensor_for_device.device).cuda_stream
         name, args = _DW_WS_NAMES[name], _with_dw_workspace(index, handle, args)

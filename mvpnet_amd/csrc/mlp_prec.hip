@@ -136,3 +136,26 @@ MVP_API int mvp_sa_train_backward_p_f32(int layer, const float* zf, const float*
       bn1_beta, W2, C2, bn2_mean, bn2_invstd, bn2_gamma, bn2_beta, W3, C3, mean_i, invstd_i, gamma_i, stat_i, dgamma_i, dbeta_i, training,
       G, pool_dout, pool_out, pool_arg, dW, lddw, dZ, stat_prev, tsum, stream));
 }
+
+MVP_API int mvp_sa_train_forward_y2_p_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float*
+    wxyz, int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd, const float* bn1_gamma,
+    const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean, const float* bn2_invstd, const float* bn2_gamma, const float*
+    bn2_beta, const float* W3, int64_t C3, double* stat, float eps, float momentum, float* mean, float* invstd, float* running_mean, float*
+    running_var, int64_t* num_batches_tracked, float* ymax, float* ymin, uint8_t* amax, uint8_t* amin, float* Y2, int precision, int
+    precision_backward, mvp_stream_t stream) {
+  MVP_WITH_PRECISION(mvp_sa_train_forward_y2_f32(stage, zf, xyz, centre, index, wxyz, B, N, M, K, C1, bn1_mean, bn1_invstd, bn1_gamma,
+      bn1_beta, W2, C2, bn2_mean, bn2_invstd, bn2_gamma, bn2_beta, W3, C3, stat, eps, momentum, mean, invstd, running_mean, running_var,
+      num_batches_tracked, ymax, ymin, amax, amin, Y2, stream));
+}
+
+MVP_API int mvp_sa_train_backward_y2_p_f32(int layer, const float* zf, const float* xyz, const float* centre, const int64_t* index, const
+    float* wxyz, int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd, const float*
+    bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean, const float* bn2_invstd, const float* bn2_gamma,
+    const float* bn2_beta, const float* W3, int64_t C3, const float* mean_i, const float* invstd_i, const float* gamma_i, const double*
+    stat_i, float* dgamma_i, float* dbeta_i, int training, const float* G, const float* pool_dout, const float* pool_out, const uint8_t*
+    pool_arg, float* dW, int64_t lddw, float* dZ, double* stat_prev, float* tsum, const float* Y2, int precision, int precision_backward,
+    mvp_stream_t stream) {
+  MVP_WITH_PRECISION(mvp_sa_train_backward_y2_f32(layer, zf, xyz, centre, index, wxyz, B, N, M, K, C1, bn1_mean, bn1_invstd, bn1_gamma,
+      bn1_beta, W2, C2, bn2_mean, bn2_invstd, bn2_gamma, bn2_beta, W3, C3, mean_i, invstd_i, gamma_i, stat_i, dgamma_i, dbeta_i, training,
+      G, pool_dout, pool_out, pool_arg, dW, lddw, dZ, stat_prev, tsum, Y2, stream));
+}

@@ -287,10 +287,11 @@ struct SaLevel {
 // check comes before any other), then the sizes, the entry point's own (`own_sizes`) included (MVP_EINVAL), then what the kernels do not
 // support (MVP_EUNSUPPORTED) -- the entry point's own conditions `own_ok` (a split-bf16 precision, alignment), the widths (C3 == 0: a pass
 // that stops at layer 2) and the limits of the 32-bit ball and row-offset arithmetic: N, M <= INT_MAX, B * M <= 2^31 - 16 (the ball loops
-// form g + 8), N * max(C1, 3) < 2^32.
+// form g + 8), N * max(C1, 3) < 2^32.  y2: the stored y_2 (B*M*32, C2) of a training pass that writes or reads it, or nullptr -- 16-byte aligned
+// rows (C2 % 4 == 0 holds for every level).
 inline int sa_level(const float* zf, bool zf_required, const float* xyz, const float* centre, const int64_t* index, const float* wxyz, int64_t B,
                     int64_t N, int64_t M, int64_t K, int64_t C1, const float* const (&bn1)[4], const float* W2, int64_t C2, int64_t C3,
-                    bool own_sizes, bool own_ok, SaLevel* lv) {
+                    bool own_sizes, bool own_ok, SaLevel* lv, const float* y2 = nullptr) {
   if (zf_required) MVP_NONNULL(zf);
   MVP_NONNULL(xyz);
   MVP_NONNULL(centre);
@@ -300,7 +301,7 @@ inline int sa_level(const float* zf, bool zf_required, const float* xyz, const f
   MVP_NONNULL(W2);
   MVP_REQUIRE(B >= 0 && N > 0 && M >= 0 && K > 0 && C1 > 0 && C2 > 0 && C3 >= 0 && own_sizes);
   const bool widths = K == 32 && C1 >= 4 && C1 <= 64 && C2 <= 64 && C3 <= 128 && C1 % 4 == 0 && C2 % 4 == 0 && C3 % 4 == 0;
-  if (!own_ok || !widths) return MVP_EUNSUPPORTED;
+  if (!own_ok || !widths || (uintptr_t)y2 % 16 != 0) return MVP_EUNSUPPORTED;
   constexpr int64_t kBalls = (int64_t(1) << 31) - 16, kOffsets = (int64_t(1) << 32) - 1;
   if (N > INT_MAX || M > INT_MAX || (M > 0 && B > kBalls / M) || N > kOffsets / std::max<int64_t>(C1, 3)) return MVP_EUNSUPPORTED;
   lv->s = SaSrc{zf, xyz, centre, index, wxyz, {bn1[0], bn1[1], bn1[2], bn1[3]}, B * M, (int)N, (int)M, (int)C1};

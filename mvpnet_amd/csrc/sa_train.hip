@@ -1,4 +1,4 @@
-// sa_train.hip -- a set-abstraction level in TRAINING mode without its (B*M*32, C) tensors, for gfx950.
+// sa_train.hip -- a set-abstraction level in TRAINING mode without its (B*M*32, C) tensors -- bar y_2 where storing it wins --, for gfx950.
 //
 // Reference shape being replaced: QueryGrouper + SharedMLP(ndim=2) + torch.max of mvpnet/models/pn2/modules.py:20-37,100-108 with
 // common/nn/modules/conv.py:41-51 in train mode (BatchNorm with BATCH statistics), forward and backward.  The unfused rows path of this
@@ -17,7 +17,20 @@
 //             pass 2  y_1, a_1, y_2 again; dz_2 loaded; dy_2; dW_2; dz_1 stored (+ sums)
 //             pass 1  per POINT through the transposed index: dy_1 from dz_1 and the re-created y_1 -> gradient of zf, gradient of the
 //                     first layer's coordinate columns, BatchNorm-1 parameter gradients  (sa_train_bwd1_kernel)
-// Only dz_2 and dz_1 of shape (B*M*32, C) ever reach HBM; y_1, y_2, y_3, dy_*, the centred coordinates never do.
+// Of the (B*M*32, C) tensors dz_2 and dz_1 always reach HBM; y_1, y_3, dy_*, the centred coordinates never do.
+// y_2 is the caller's choice, pass by pass (the Y2 argument of the _y2 entry points; rows.SA_Y2_PASSES holds the measured choice):
+// re-creating it is the most expensive link of the chain -- gather, first layer, BatchNorm + ReLU, a 3-piece split and six MFMA products per
+// slab, in the backward too, whose ReLU masks must be the forward's -- and three passes repeat it.  So forward pass 2 may STORE y_2 (fp32,
+// through the wave's tile, next to its statistics), and pass 3 and the two backward passes may LOAD it in accumulator layout instead:
+//   pass 3            no level input, no image of W_2, no first-layer tables: y_2 -> a_2 -> y_3, the next ball's y_2 in flight
+//   backward pass 3   the same front end gone, and 6 - 24 KB of LDS with the image of W_2
+//   backward pass 2   keeps the gather (y_1 and the centred coordinates), loads y_2 per channel block beside dz_2; no act_rows, no 3-piece MFMA
+// The stored values are the re-created ones bit for bit (pass 3 repeats pass 2's code; the backward re-computes with the forward's pieces),
+// and a loading pass launches the re-computing pass' grid, so every per-row and per-ball result and every partial sum is unchanged.
+// Measured at B = 32 of the reference network (profiles/sa_y2.txt): pass 3 136 -> 98 us (level 1) and 135 -> 95 us (level 2), backward pass 3
+// 217 -> 173 and 235 -> 183 - 199 us, the store 35 us at level 1 (268 MB) and free at level 2; backward pass 2 LOSES at level 1 (157 -> 178 us: it
+// reads dz_2 at 0.7 of the HBM peak already) and gains less than its spread at level 2, so it re-computes by default.  The re-computing
+// instances stay for every pass: the default for all other shapes, and the fallback.
 //
 // Layouts (as sa_fused.hip / mlp_bwd.hip): one wave = one ball.  "Row layout": lane (li = lane & 31 = neighbour, lh = lane >> 5) holds
 // channels k = 32 sl + 8 tt + 4 lh + e of its row -- the A fragments of v_mfma_f32_32x32x16_bf16.  "Accumulator layout": lane = channel
@@ -83,6 +96,91 @@ __device__ __forceinline__ void stats_tail(const float (&ssum)[NB], const float 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// the stored y_2: Y2 (R, C2) float32, written by forward pass 2 and read by the passes that do not re-create it
+// ---------------------------------------------------------------------------------------------------------------------------------
+// what a pass does with y_2: re-creates it and keeps it in registers; (stage 2) also writes it to Y2; reads it from Y2 instead
+enum { kY2Recompute = 0, kY2Store = 1, kY2Load = 2 };
+
+#ifndef MVP_SA_Y2_NT   // 1: non-temporal stores of y_2 (A/B build; the measurement is in profiles/sa_y2.txt)
+#define MVP_SA_Y2_NT 0
+#endif
+
+// y_2 of ball g in accumulator layout <-> rows 32 g .. 32 g + 31 of Y2.
+// Store: through the wave-private tile into 16-byte stores, eight full rows per instruction, as the dz epilogue of the backward (stored
+// straight from the accumulator layout -- 16 four-byte stores per block with an address each -- stage 2 of the (64, 64) level spilled).
+// Load: lane = column, register q = row acc_row(q, h), so a wave instruction covers two full 128-byte rows (as load_g of the backward
+// reads dz_2).  Columns >= C2 are not stored and are loaded as a copy of column C2 - 1: every user masks them or meets them with a zero
+// weight, as it does the zeros a re-computation leaves there.
+template <int C2B>
+__device__ __forceinline__ void y2_store(float* Y2, int g, int C2, float* st, int lane, const f32x16 (&y)[C2B]) {
+  const int c = lane & 31, h = lane >> 5;
+  float* Yt = Y2 + (size_t)g * 32 * C2;
+#pragma unroll
+  for (int b = 0; b < C2B; ++b) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) st[acc_row(q, h) * kFLd + c] = y[b][q];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int pp = 0; pp < 4; ++pp) {
+      const int row = pp * 8 + (lane >> 3), c4 = (lane & 7) * 4;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(st + row * kFLd + c4);
+      const int cc = 32 * b + c4;
+      if (cc < C2) {  // C2 % 4 == 0
+#if MVP_SA_Y2_NT
+        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(Yt + (unsigned)(row * C2 + cc)));
+#else
+        *reinterpret_cast<f32x4*>(Yt + (unsigned)(row * C2 + cc)) = v;
+#endif
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+__device__ __forceinline__ void y2_load_block(const float* Y2, int g, int C2, int b, int c, int h, float (&y)[16]) {
+  const float* Yt = Y2 + (size_t)g * 32 * C2;
+  const int col = min(32 * b + c, C2 - 1);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) y[q] = Yt[(unsigned)(acc_row(q, h) * C2 + col)];
+}
+template <int C2B>
+__device__ __forceinline__ void y2_load(const float* Y2, int g, int C2, int c, int h, f32x16 (&y)[C2B]) {
+#pragma unroll
+  for (int b = 0; b < C2B; ++b) {
+    float v[16];
+    y2_load_block(Y2, g, C2, b, c, h, v);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) y[b][q] = v[q];
+  }
+}
+
+// The balls of a wave, as BallPipe, for a pass whose only per-ball input is the stored y_2: with PF the loads of ball g + 4 are in flight
+// while ball g is worked on.
+//   Y2Pipe<..> pipe;  for (int g = pipe.begin(Y2, G, tiles_per_wg, C2, wave, c, h); g < pipe.t_end; g += 4) { pipe.rows(Y2, g, C2, c, h, y2); ... }
+template <int C2B, bool PF>
+struct Y2Pipe {
+  f32x16 yn[C2B];   // PF: y_2 of the next ball
+  int64_t t_end;
+  __device__ __forceinline__ int begin(const float* Y2, int64_t G, int64_t tiles_per_wg, int C2, int wave, int c, int h) {
+    const int64_t t_begin = (int64_t)blockIdx.x * tiles_per_wg;
+    t_end = min(G, t_begin + tiles_per_wg);
+    const int g = __builtin_amdgcn_readfirstlane((int)(t_begin + wave));
+    if constexpr (PF) {
+      if (g < t_end) y2_load<C2B>(Y2, g, C2, c, h, yn);
+    }
+    return g;
+  }
+  __device__ __forceinline__ void rows(const float* Y2, int g, int C2, int c, int h, f32x16 (&y)[C2B]) {
+    if constexpr (PF) {
+#pragma unroll
+      for (int b = 0; b < C2B; ++b) y[b] = yn[b];
+      if (g + 4 < t_end) y2_load<C2B>(Y2, g + 4, C2, c, h, yn);
+    } else {
+      y2_load<C2B>(Y2, g, C2, c, h, y);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // forward passes 2 and 3
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct SaFwdArgs {
@@ -97,30 +195,39 @@ struct SaFwdArgs {
   float* ymin;
   uint8_t* amax;
   uint8_t* amin;
+  float* Y2;            // (R, C2): written (kY2Store, stage 2) or read (kY2Load, stage 3)
   int64_t tiles_per_wg;
 };
 
 // Prefetch of the next ball's rows (measured per pass on level 1 of the reference network, tools/exp/sa_train_ab.sh): it pays where the
 // registers are there -- stage 2 (95 -> 77 us) and the layer-3 backward (249 -> 235 us) -- and costs a wave per SIMD or spills where they are
-// not: stage 3 (144 -> 178 us) and the layer-2 backward (345 -> 369 us) load every ball's rows when they work on it.
-template <int C1B, int C2B, int C3B, int NS, int STAGE>
-__global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
+// not: stage 3 (144 -> 178 us) and the layer-2 backward (345 -> 369 us) load every ball's rows when they work on it.  (A stage 3 that
+// loads y_2 has the registers of the rows free: it keeps the next ball's y_2 in flight.)
+// Y2M == kY2Load (stage 3): the pass has no front end at all -- no level input, no image of W_2, no first-layer tables; y_2 arrives in
+// accumulator layout straight from memory, and the registers the ball's rows held go to the next ball's y_2.
+template <int C1B, int C2B, int C3B, int NS, int STAGE, int Y2M>
+__device__ __forceinline__ void sa_train_fwd_pass(const SaFwdArgs& p) {
+  static_assert(Y2M == kY2Recompute || (Y2M == kY2Store && STAGE == 2) || (Y2M == kY2Load && STAGE == 3), "stage 2 stores y_2, stage 3 loads it");
+  constexpr bool LOAD = Y2M == kY2Load;
   constexpr bool PF = STAGE == 2;
-  constexpr int kW2 = C1B * NS * C2B * 32 * 64;
+  constexpr bool PFY = C2B * C3B < 8 || NS > 1;   // the next ball's y_2 in flight (not at (64, 64, 128) with two workgroups per CU: no registers)
+  constexpr int kW2 = LOAD ? 16 : C1B * NS * C2B * 32 * 64;
   constexpr int kW3 = STAGE == 3 ? C2B * NS * C3B * 32 * 64 : 16;
   constexpr int NBS = STAGE == 3 ? C3B : C2B;
   __shared__ __attribute__((aligned(16))) unsigned char W2l[kW2];
   __shared__ __attribute__((aligned(16))) unsigned char W3l[kW3];
-  __shared__ __attribute__((aligned(16))) float P1[4 * C1B * 32];
-  __shared__ __attribute__((aligned(16))) float Wx[C1B * 32][4];
+  __shared__ __attribute__((aligned(16))) float P1[LOAD ? 4 : 4 * C1B * 32];
+  __shared__ __attribute__((aligned(16))) float Wx[LOAD ? 1 : C1B * 32][4];
   __shared__ __attribute__((aligned(16))) float tiles[4][32 * kFLd];
   __shared__ double sred[2][4][NBS * 32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int C1 = p.s.C1, C2 = p.C2, C3 = p.C3;
-  stage_weight<NS>(W2l, p.W2, C2, C1, C2B * 32, C1B, tid);
+  if constexpr (!LOAD) {
+    stage_weight<NS>(W2l, p.W2, C2, C1, C2B * 32, C1B, tid);
+    stage_layer1<C1B>(p.s, P1, Wx, tid);
+  }
   if constexpr (STAGE == 3) stage_weight<NS>(W3l, p.W3, C3, C2, C3B * 32, C2B, tid);
-  stage_layer1<C1B>(p.s, P1, Wx, tid);
   LaneBn<C2B> bn2;
   if constexpr (STAGE == 3) bn2.load(p.bn2, C2, li);
   float ssum[NBS], qsum[NBS];
@@ -129,14 +236,24 @@ __global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
   __syncthreads();
   float* st = tiles[wave];
   BallPipe<C1B, PF> pipe;
-  for (int g = pipe.begin(p.s, p.tiles_per_wg, wave, li, lh); g < pipe.t_end; g += 4) {
-    BallRows<C1B> rc;
-    pipe.rows(p.s, g, li, lh, rc);
-    float v1[C1B][4][4], dif[3];
-    gather_finish<C1B>(rc, lh, Wx, v1, dif);
-    act_rows<C1B>(v1, P1, lh);
+  Y2Pipe<C2B, PFY> ypipe;
+  int g;
+  if constexpr (LOAD) g = ypipe.begin(p.Y2, p.s.G, p.tiles_per_wg, C2, wave, li, lh);
+  else g = pipe.begin(p.s, p.tiles_per_wg, wave, li, lh);
+  const int64_t t_end = LOAD ? ypipe.t_end : pipe.t_end;
+  for (; g < t_end; g += 4) {
     f32x16 acc2[C2B];
-    layer_mfma<C1B, C2B, NS>(v1, W2l, li, lh, acc2);
+    if constexpr (LOAD) {
+      ypipe.rows(p.Y2, g, C2, li, lh, acc2);
+    } else {
+      BallRows<C1B> rc;
+      pipe.rows(p.s, g, li, lh, rc);
+      float v1[C1B][4][4], dif[3];
+      gather_finish<C1B>(rc, lh, Wx, v1, dif);
+      act_rows<C1B>(v1, P1, lh);
+      layer_mfma<C1B, C2B, NS>(v1, W2l, li, lh, acc2);
+    }
+    if constexpr (Y2M == kY2Store) y2_store<C2B>(p.Y2, g, C2, st, lane, acc2);
     if constexpr (STAGE == 2) {
 #pragma unroll
       for (int jb = 0; jb < C2B; ++jb) {
@@ -204,6 +321,18 @@ __global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
   stats_tail<NBS>(ssum, qsum, sred, p.stat, STAGE == 3 ? C3 : C2, p.fin, true);
 }
 
+template <int C1B, int C2B, int C3B, int NS, int STAGE>
+__global__ __launch_bounds__(kFT) void sa_train_fwd_kernel(SaFwdArgs p) {
+  sa_train_fwd_pass<C1B, C2B, C3B, NS, STAGE, kY2Recompute>(p);
+}
+// (launch bounds of a stage 3 that loads: the workgroups per CU of the re-computing stage 3 -- the entry point launches the same grid, so
+// that the statistics' fp32 partial sums stay the same --, which is ONE for (64, 64, 128) with a split precision: the next ball's y_2 is
+// then in flight; left alone the compiler spends a single wave's register budget on hoisted loads elsewhere, as in the backward below)
+template <int C1B, int C2B, int C3B, int NS, int STAGE, int Y2M>
+__global__ __launch_bounds__(kFT, (Y2M != kY2Load ? 1 : C2B * C3B >= 8 ? (NS == 1 ? 2 : 1) : C2B == 2 ? 2 : 3)) void sa_train_fwd_y2_kernel(SaFwdArgs p) {
+  sa_train_fwd_pass<C1B, C2B, C3B, NS, STAGE, Y2M>(p);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // backward passes 3 and 2: mlp_bwd_layer_kernel's choreography (dW from the registers as they are, dz through the wave-private tile,
 // ReLU mask + BatchNorm-backward column sums against the x still in registers) with x -- and the y_i of the "finish" -- re-created per
@@ -233,6 +362,7 @@ struct SaBwdArgs {
   float* dZ;             // (R, Cp) out: dz_{i-1}
   double* stat_prev;     // (2 Cp) accumulated into (fp64 atomics by the <= 1024 workgroups)
   float* tsum;           // LAYER 2: (16 slots, C1, 4) += sum over the rows of dz_1[e][c] * (xyz[j_e] - centre)[k]  (operand of the coordinate columns' gradient)
+  const float* Y2;       // Y2L: the forward's y_2 (R, C2)
   int64_t tiles_per_wg;
 };
 
@@ -240,15 +370,21 @@ struct SaBwdArgs {
 // fraction f of the elements costs ~sqrt(f) of the gradient's norm (measured: 3.5e-3 with y_2 re-computed in 2 pieces against the forward's
 // 3): with NSF = the FORWARD pieces the re-computed y_2 is the forward's bit for bit; only the gradient contractions (dW, dz -- and y_3,
 // which feeds xhat_3 alone: the pooled mask comes from the stored output) run with the NS backward pieces.
-// (two workgroups per CU for the narrow variants: left alone the compiler spends the whole 512-register budget of a single wave per SIMD
+// (two workgroups per CU for the narrow variants -- bar the (32, 64, 32) layer-3 pass that loads y_2: it spills at that --: left alone the
+// compiler spends the whole 512-register budget of a single wave per SIMD
 // on hoisted loads -- 254 + 32 registers for the (32, 32) layer-2 pass -- and the pass, bound by exposed latency, takes twice as long)
-template <int C1B, int C2B, int C3B, int NS, int LAYER, int NSF>
-__global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2B == 1) ? 2 : 1)) void sa_train_bwd_kernel(SaBwdArgs p) {
+// Y2L: y_2 is loaded from the forward's Y2 instead (NSF then has no say; the entry point instantiates NSF = NS).  The image W2f, act_rows
+// and the NSF layer_mfma are gone; LAYER 3 has no front end left at all (x = y_2 arrives in accumulator layout straight from memory, the
+// next ball's in flight), LAYER 2 keeps the gather for y_1 and the centred coordinates and loads y_2 per channel block beside dz_2.
+template <int C1B, int C2B, int C3B, int NS, int LAYER, int NSF, bool Y2L>
+__device__ __forceinline__ void sa_train_bwd_pass(const SaBwdArgs& p) {
   using SP = SplitPairs<NS>;
   constexpr bool PF = LAYER == 3;
+  constexpr bool NOROWS = Y2L && LAYER == 3;     // no gather: the pass works from the stored y_2 alone
+  constexpr bool PFY = NS < 3 && C2B <= C1B;     // NOROWS: the next ball's y_2 in flight where the registers are there (the others spill with it)
   constexpr int CB = LAYER == 3 ? C3B : C2B;     // channel blocks of dy_i
   constexpr int CPB = LAYER == 3 ? C2B : C1B;    // channel blocks of x = y_{i-1}
-  constexpr int kW2f = C1B * NSF * C2B * 32 * 64;                      // forward image of W_2 (y_2 again)
+  constexpr int kW2f = Y2L ? 0 : C1B * NSF * C2B * 32 * 64;            // forward image of W_2 (y_2 again)
   constexpr int kW3f = LAYER == 3 ? C2B * NS * C3B * 32 * 64 : 0;      // forward image of W_3 (y_3 again)
   constexpr int kWb = NS * CB * CPB * 32 * 64;                         // backward image of W_i (dz_{i-1} = dy_i . W_i)
   constexpr int kTileBytes = 4 * 32 * kFLd * 4;
@@ -256,8 +392,8 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
   constexpr int kMain = kW2f + kW3f + kWb + kTileBytes;
   constexpr int kLds = kMain > kRedBytes ? kMain : kRedBytes;
   __shared__ __attribute__((aligned(16))) unsigned char lds[kLds];
-  __shared__ __attribute__((aligned(16))) float P1[4 * C1B * 32];
-  __shared__ __attribute__((aligned(16))) float Wx[C1B * 32][4];
+  __shared__ __attribute__((aligned(16))) float P1[NOROWS ? 4 : 4 * C1B * 32];
+  __shared__ __attribute__((aligned(16))) float Wx[NOROWS ? 1 : C1B * 32][4];
   __shared__ __attribute__((aligned(16))) float dtile[4][32][4];   // LAYER 2: the ball's centred coordinates by row
   __shared__ double sred[2][4][CPB * 32];
   unsigned char* W2f = lds;
@@ -270,9 +406,9 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
   const int C = LAYER == 3 ? C3 : C2, Cp = LAYER == 3 ? C2 : C1;
   const float* W = LAYER == 3 ? p.W3 : p.W2;   // (C, Cp)
 
-  stage_weight<NSF>(W2f, p.W2, C2, C1, C2B * 32, C1B, tid);
+  if constexpr (!Y2L) stage_weight<NSF>(W2f, p.W2, C2, C1, C2B * 32, C1B, tid);
   if constexpr (LAYER == 3) stage_weight<NS>(W3f, p.W3, C3, C2, C3B * 32, C2B, tid);
-  stage_layer1<C1B>(p.s, P1, Wx, tid);
+  if constexpr (!NOROWS) stage_layer1<C1B>(p.s, P1, Wx, tid);
   {  // W_i -> LDS, split, fragment order of the dz contraction (thread: (c_in, quad of 4 consecutive c_out)), as mlp_bwd_layer_kernel
     const int quads = CB * 8;
     for (int t = tid; t < quads * CPB * 32; t += kFT) {
@@ -345,39 +481,49 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
   __syncthreads();
 
   BallPipe<C1B, PF> pipe;
-  for (int g = pipe.begin(p.s, p.tiles_per_wg, wave, c, h); g < pipe.t_end; g += 4) {
-    BallRows<C1B> rc;
-    pipe.rows(p.s, g, c, h, rc);
-    float gn[16];
+  Y2Pipe<C2B, PFY> ypipe;
+  int g;
+  if constexpr (NOROWS) g = ypipe.begin(p.Y2, p.s.G, p.tiles_per_wg, C2, wave, c, h);
+  else g = pipe.begin(p.s, p.tiles_per_wg, wave, c, h);
+  const int64_t t_end = NOROWS ? ypipe.t_end : pipe.t_end;
+  for (; g < t_end; g += 4) {
+    float gn[16], yn[16];
     auto load_g = [&](int a) {  // LAYER 2: channel block a of dz_2 of this ball, accumulator layout (two full 128-byte rows per instruction)
       const float* Gt = p.G + (size_t)g * 32 * C;
       const int col = min(32 * a + c, C - 1);
 #pragma unroll
       for (int q = 0; q < 16; ++q) gn[q] = Gt[(unsigned)(acc_row(q, h) * C + col)];
+      if constexpr (Y2L) y2_load_block(p.Y2, g, C2, a, c, h, yn);   // ... and of the stored y_2
     };
-    if constexpr (LAYER == 2) load_g(0);
     // ---- the ball's y_1 (row layout), then x = y_{i-1} in accumulator layout and, for LAYER 2, y_2 in accumulator layout
-    float v1[C1B][4][4], dif[3];
-    gather_finish<C1B>(rc, h, Wx, v1, dif);
-    if constexpr (LAYER == 2) {
-      if (h == 0) *reinterpret_cast<float4*>(&dtile[wave][c][0]) = make_float4(dif[0], dif[1], dif[2], 0.f);
-    }
     float x[CPB][16];
     f32x16 y2[C2B];
-    if constexpr (LAYER == 2) {
+    if constexpr (NOROWS) {
+      ypipe.rows(p.Y2, g, C2, c, h, y2);
+    } else {
+      BallRows<C1B> rc;
+      pipe.rows(p.s, g, c, h, rc);
+      if constexpr (LAYER == 2) load_g(0);
+      float v1[C1B][4][4], dif[3];
+      gather_finish<C1B>(rc, h, Wx, v1, dif);
+      if constexpr (LAYER == 2) {
+        if (h == 0) *reinterpret_cast<float4*>(&dtile[wave][c][0]) = make_float4(dif[0], dif[1], dif[2], 0.f);
 #pragma unroll
-      for (int sl = 0; sl < C1B; ++sl) {  // y_1: rows -> accumulator layout through the tile
+        for (int sl = 0; sl < C1B; ++sl) {  // y_1: rows -> accumulator layout through the tile
 #pragma unroll
-        for (int tt = 0; tt < 4; ++tt)
-          *reinterpret_cast<float4*>(tile + c * kFLd + 8 * tt + 4 * h) = make_float4(v1[sl][tt][0], v1[sl][tt][1], v1[sl][tt][2], v1[sl][tt][3]);
-        __builtin_amdgcn_wave_barrier();
+          for (int tt = 0; tt < 4; ++tt)
+            *reinterpret_cast<float4*>(tile + c * kFLd + 8 * tt + 4 * h) = make_float4(v1[sl][tt][0], v1[sl][tt][1], v1[sl][tt][2], v1[sl][tt][3]);
+          __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int q = 0; q < 16; ++q) x[sl][q] = tile[acc_row(q, h) * kFLd + c];
-        __builtin_amdgcn_wave_barrier();
+          for (int q = 0; q < 16; ++q) x[sl][q] = tile[acc_row(q, h) * kFLd + c];
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+      if constexpr (!Y2L) {
+        act_rows<C1B>(v1, P1, h);
+        layer_mfma<C1B, C2B, NSF>(v1, W2f, c, h, y2);
       }
     }
-    act_rows<C1B>(v1, P1, h);
-    layer_mfma<C1B, C2B, NSF>(v1, W2f, c, h, y2);
     if constexpr (LAYER == 3) {
 #pragma unroll
       for (int b = 0; b < CPB; ++b)
@@ -454,7 +600,7 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
       } else {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const float xh = (y2[a][q] - mu[a]) * is[a];
+          const float xh = ((Y2L ? yn[q] : y2[a][q]) - mu[a]) * is[a];
           const float d = sc[a] * ((gn[q] - db[a]) - xh * dg[a]);
           dyv[q] = cok[a] ? d : 0.f;
         }
@@ -591,6 +737,15 @@ __global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2
         }
       }
   }
+}
+
+template <int C1B, int C2B, int C3B, int NS, int LAYER, int NSF>
+__global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 : C1B * C2B == 1) ? 2 : 1)) void sa_train_bwd_kernel(SaBwdArgs p) {
+  sa_train_bwd_pass<C1B, C2B, C3B, NS, LAYER, NSF, false>(p);
+}
+template <int C1B, int C2B, int C3B, int NS, int LAYER>
+__global__ __launch_bounds__(kFT, ((LAYER == 3 ? C1B * C2B * C3B <= 2 && C2B <= C1B : C1B * C2B == 1) ? 2 : 1)) void sa_train_bwd_y2_kernel(SaBwdArgs p) {
+  sa_train_bwd_pass<C1B, C2B, C3B, NS, LAYER, NS, true>(p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -881,13 +1036,15 @@ __global__ __launch_bounds__(256) void sa_train_bwd1_kernel(SaBwd1Args p) {
 // stat: 2*C + 1 float64, ALL zero on entry (C = C2 / C3): column sums of y, of y^2, completion counter (zero again on exit).
 // Needs K == 32, C1, C2 <= 64, C3 <= 64 (or exactly the (<= 64, <= 64, <= 128) block shape with C1, C2 > 32), multiples of 4, a split-bf16
 // precision, sizes within the limits of sa_level (sa_common.h): MVP_EUNSUPPORTED otherwise.
-MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
+// Y2 (B*M*32, C2) float32, 16-byte aligned, or NULL: stage 2 also WRITES y_2 there; stage 3 READS it instead of re-creating it from the level's
+// input (same values bit for bit: it repeats stage 2's code).  NULL: mvp_sa_train_forward_f32.
+MVP_API int mvp_sa_train_forward_y2_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
                                      int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
                                      const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,
                                      const float* bn2_invstd, const float* bn2_gamma, const float* bn2_beta, const float* W3, int64_t C3,
                                      double* stat, float eps, float momentum, float* mean, float* invstd, float* running_mean,
                                      float* running_var, int64_t* num_batches_tracked, float* ymax, float* ymin, uint8_t* amax,
-                                     uint8_t* amin, mvp_stream_t stream) {
+                                     uint8_t* amin, float* Y2, mvp_stream_t stream) {
   MVP_NONNULL(stat);
   MVP_NONNULL(mean);
   MVP_NONNULL(invstd);
@@ -907,23 +1064,44 @@ MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xy
   const int ns = mlp_fwd_pieces();
   SaLevel lv;
   const int rc = sa_level(zf, true, xyz, centre, index, wxyz, B, N, M, K, C1, {bn1_mean, bn1_invstd, bn1_gamma, bn1_beta}, W2, C2, C3,
-                          sizes, ns != 0 && (uintptr_t)zf % 16 == 0, &lv);
+                          sizes, ns != 0 && (uintptr_t)zf % 16 == 0, &lv, Y2);
   if (rc != MVP_OK || lv.s.G == 0) return rc;
   SaFwdArgs a{lv.s, W2, {bn2_mean, bn2_invstd, bn2_gamma, bn2_beta}, W3, (int)C2, (int)C3, stat,
-              BnFinalize{B * M * K, eps, momentum, mean, invstd, running_mean, running_var, num_batches_tracked}, ymax, ymin, amax, amin, 0};
-  const int64_t lds = (int64_t)ns * 2048 * (lv.c1b * lv.c2b + (stage == 3 ? lv.c2b * lv.c3b : 0)) + 32 * 1024;
-  const unsigned grid = sa_grid(lv.s.G, lds, 4, 1024, &a.tiles_per_wg);
+              BnFinalize{B * M * K, eps, momentum, mean, invstd, running_mean, running_var, num_batches_tracked}, ymax, ymin, amax, amin, Y2, 0};
+  // LDS: the images + tiles, tables and the statistics' reduction; a stage 3 that loads y_2 holds W_3's image, the tiles (18 KB) and the
+  // reduction (2 KB per block of C3) alone.  It still launches the grid of the re-computing stage 3 (no more workgroups per CU than that
+  // one's LDS lets in): which balls a wave walks decides its fp32 partial sums of the statistics, and with the same grid mean and invstd --
+  // and everything behind them -- are what re-computation gives, bit for bit up to the fp64 atomics' order.
+  const bool load = Y2 && stage == 3;
+  const int64_t lds_re = (int64_t)ns * 2048 * (lv.c1b * lv.c2b + (stage == 3 ? lv.c2b * lv.c3b : 0)) + 32 * 1024;
+  const int64_t lds = load ? (int64_t)ns * 2048 * lv.c2b * lv.c3b + 18 * 1024 + 2048 * lv.c3b + 1024 : lds_re;
+  const unsigned grid = sa_grid(lv.s.G, lds, std::max<int64_t>(1, std::min<int64_t>(4, (150 * 1024) / lds_re)), 1024, &a.tiles_per_wg);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  auto launch = [&](auto shapes, auto st) {
+  auto launch = [&](auto shapes, auto st, auto y2m) {
     return sa_pick(shapes, {lv.c1b, lv.c2b, lv.c3b}, [&](auto sh) {
       sa_pick(SaPieces{}, {ns}, [&](auto pc) {
-        hipLaunchKernelGGL((sa_train_fwd_kernel<decltype(sh)::v[0], decltype(sh)::v[1], decltype(sh)::v[2], decltype(pc)::v[0], decltype(st)::v[0]>),
-                           dim3(grid), dim3(kFT), 0, s, a);
+        constexpr int c1 = decltype(sh)::v[0], c2 = decltype(sh)::v[1], c3 = decltype(sh)::v[2], np = decltype(pc)::v[0], sg = decltype(st)::v[0];
+        constexpr int ym = decltype(y2m)::v[0];
+        if constexpr (ym == kY2Recompute) hipLaunchKernelGGL((sa_train_fwd_kernel<c1, c2, c3, np, sg>), dim3(grid), dim3(kFT), 0, s, a);
+        else hipLaunchKernelGGL((sa_train_fwd_y2_kernel<c1, c2, c3, np, sg, ym>), dim3(grid), dim3(kFT), 0, s, a);
       });
     });
   };
-  const bool found = stage == 3 ? launch(SaShapes3{}, SaRow<3>{}) : launch(SaShapes2{}, SaRow<2>{});
+  const bool found = stage == 3 ? (Y2 ? launch(SaShapes3{}, SaRow<3>{}, SaRow<kY2Load>{}) : launch(SaShapes3{}, SaRow<3>{}, SaRow<kY2Recompute>{}))
+                                : (Y2 ? launch(SaShapes2{}, SaRow<2>{}, SaRow<kY2Store>{}) : launch(SaShapes2{}, SaRow<2>{}, SaRow<kY2Recompute>{}));
   return found ? mvp_launch_status() : MVP_EUNSUPPORTED;
+}
+
+MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xyz, const float* centre, const int64_t* index, const float* wxyz,
+                                     int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean, const float* bn1_invstd,
+                                     const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2, const float* bn2_mean,
+                                     const float* bn2_invstd, const float* bn2_gamma, const float* bn2_beta, const float* W3, int64_t C3,
+                                     double* stat, float eps, float momentum, float* mean, float* invstd, float* running_mean,
+                                     float* running_var, int64_t* num_batches_tracked, float* ymax, float* ymin, uint8_t* amax,
+                                     uint8_t* amin, mvp_stream_t stream) {
+  return mvp_sa_train_forward_y2_f32(stage, zf, xyz, centre, index, wxyz, B, N, M, K, C1, bn1_mean, bn1_invstd, bn1_gamma, bn1_beta, W2, C2, bn2_mean,
+                                     bn2_invstd, bn2_gamma, bn2_beta, W3, C3, stat, eps, momentum, mean, invstd, running_mean, running_var,
+                                     num_batches_tracked, ymax, ymin, amax, amin, nullptr, stream);   // (every pass re-creates y_2)
 }
 
 // Backward pass of layer 3 (layer == 3) or layer 2 (layer == 2) of the level (see the top of the file).  Level input and bn1 / W2 / bn2
@@ -933,14 +1111,16 @@ MVP_API int mvp_sa_train_forward_f32(int stage, const float* zf, const float* xy
 //   layer 3: pool_dout / pool_out / pool_arg (B*M, C3) -> dW (C3, lddw >= C2) +=, dZ (B*M*32, C2) = dz_2, stat_prev (2 C2) +=
 //   layer 2: G = dz_2 (B*M*32, C2)                    -> dW (C2, lddw >= C1) +=, dZ (B*M*32, C1) = dz_1, stat_prev (2 C1) +=,
 //            tsum (16, C1, 4) float32 += (in 16 slots) sum over the rows of dz_1[e][c] * (xyz[j_e] - centre)[k]  (for mvp_sa_train_backward1_f32)
-MVP_API int mvp_sa_train_backward_f32(int layer, const float* zf, const float* xyz, const float* centre, const int64_t* index,
+// Y2 (B*M*32, C2) float32, 16-byte aligned, or NULL: the y_2 that mvp_sa_train_forward_y2_f32(stage 2) stored, read instead of re-created
+// (dz the same bit for bit: the re-computation uses the forward's pieces).  NULL: mvp_sa_train_backward_f32.
+MVP_API int mvp_sa_train_backward_y2_f32(int layer, const float* zf, const float* xyz, const float* centre, const int64_t* index,
                                       const float* wxyz, int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean,
                                       const float* bn1_invstd, const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2,
                                       const float* bn2_mean, const float* bn2_invstd, const float* bn2_gamma, const float* bn2_beta,
                                       const float* W3, int64_t C3, const float* mean_i, const float* invstd_i, const float* gamma_i,
                                       const double* stat_i, float* dgamma_i, float* dbeta_i, int training, const float* G,
                                       const float* pool_dout, const float* pool_out, const uint8_t* pool_arg, float* dW, int64_t lddw,
-                                      float* dZ, double* stat_prev, float* tsum, mvp_stream_t stream) {
+                                      float* dZ, double* stat_prev, float* tsum, const float* Y2, mvp_stream_t stream) {
   MVP_NONNULL(mean_i);
   MVP_NONNULL(invstd_i);
   MVP_NONNULL(gamma_i);
@@ -966,31 +1146,48 @@ MVP_API int mvp_sa_train_backward_f32(int layer, const float* zf, const float* x
   const int ns = mlp_bwd_pieces();
   SaLevel lv;
   const int rc = sa_level(zf, true, xyz, centre, index, wxyz, B, N, M, K, C1, {bn1_mean, bn1_invstd, bn1_gamma, bn1_beta}, W2, C2, C3,
-                          sizes, ns != 0 && (uintptr_t)zf % 16 == 0 && (uintptr_t)dZ % 16 == 0, &lv);
+                          sizes, ns != 0 && (uintptr_t)zf % 16 == 0 && (uintptr_t)dZ % 16 == 0, &lv, Y2);
   if (rc != MVP_OK || lv.s.G == 0) return rc;
   SaBwdArgs a{lv.s, W2, {bn2_mean, bn2_invstd, bn2_gamma, bn2_beta}, W3, (int)C2, (int)C3, mean_i, invstd_i, gamma_i, stat_i,
               dbeta_i ? dgamma_i : nullptr, dbeta_i, training ? 1.0f / (float)(B * M * K) : 0.f, G, pool_dout, pool_out, pool_arg, dW, (int)lddw, dZ,
-              stat_prev, tsum, 0};
+              stat_prev, tsum, Y2, 0};
   const int c1b = lv.c1b, c2b = lv.c2b, c3b = lv.c3b;
   const int cb = layer == 3 ? c3b : c2b, cpb = layer == 3 ? c2b : c1b;
-  // y_2 is re-computed with the forward's pieces when those are 3 (the default: forward bf16x6, backward bf16x3), else with the backward's
-  const int nsf = (mlp_fwd_pieces() == 3) ? 3 : ns;
-  const int64_t lds = (int64_t)2048 * (nsf * c1b * c2b + ns * ((layer == 3 ? c2b * c3b : 0) + cb * cpb)) + 32 * 1024;
+  // y_2 is re-computed with the forward's pieces when those are 3 (the default: forward bf16x6, backward bf16x3), else with the backward's;
+  // a loaded y_2 has the forward's pieces in it already, and the image of W_2 is not staged
+  const int nsf = (mlp_fwd_pieces() == 3 && !Y2) ? 3 : ns;
+  const int64_t lds = (int64_t)2048 * ((Y2 ? 0 : nsf * c1b * c2b) + ns * ((layer == 3 ? c2b * c3b : 0) + cb * cpb)) + 32 * 1024;
   // (registers: two workgroups per CU for the narrow variants -- the kernel's launch bounds --, one for the others)
-  const bool narrow = layer == 3 ? c1b * c2b * c3b <= 2 : c1b * c2b == 1;
+  const bool narrow = layer == 3 ? c1b * c2b * c3b <= 2 && (!Y2 || c2b <= c1b) : c1b * c2b == 1;
   const unsigned grid = sa_grid(lv.s.G, lds, narrow ? 2 : 1, 1024, &a.tiles_per_wg);
   hipStream_t s = static_cast<hipStream_t>(stream);
   using Pieces = SaTable<SaRow<1, 1>, SaRow<1, 3>, SaRow<2, 2>, SaRow<2, 3>, SaRow<3, 3>>;   // (NS, NSF)
-  auto launch = [&](auto shapes, auto ly) {
+  using PiecesY2 = SaTable<SaRow<1, 1>, SaRow<2, 2>, SaRow<3, 3>>;
+  auto launch = [&](auto shapes, auto ly, auto pieces, auto y2l) {
     return sa_pick(shapes, {c1b, c2b, c3b}, [&](auto sh) {
-      sa_pick(Pieces{}, {ns, nsf}, [&](auto pc) {
-        hipLaunchKernelGGL((sa_train_bwd_kernel<decltype(sh)::v[0], decltype(sh)::v[1], decltype(sh)::v[2], decltype(pc)::v[0], decltype(ly)::v[0],
-                                                decltype(pc)::v[1]>), dim3(grid), dim3(kFT), 0, s, a);
+      sa_pick(pieces, {ns, nsf}, [&](auto pc) {
+        constexpr int c1 = decltype(sh)::v[0], c2 = decltype(sh)::v[1], c3 = decltype(sh)::v[2], np = decltype(pc)::v[0], lr = decltype(ly)::v[0];
+        if constexpr (decltype(y2l)::v[0] != 0) hipLaunchKernelGGL((sa_train_bwd_y2_kernel<c1, c2, c3, np, lr>), dim3(grid), dim3(kFT), 0, s, a);
+        else hipLaunchKernelGGL((sa_train_bwd_kernel<c1, c2, c3, np, lr, decltype(pc)::v[1]>), dim3(grid), dim3(kFT), 0, s, a);
       });
     });
   };
-  const bool found = layer == 3 ? launch(SaShapes3{}, SaRow<3>{}) : launch(SaShapes2{}, SaRow<2>{});
+  const bool found = layer == 3 ? (Y2 ? launch(SaShapes3{}, SaRow<3>{}, PiecesY2{}, SaRow<1>{}) : launch(SaShapes3{}, SaRow<3>{}, Pieces{}, SaRow<0>{}))
+                                : (Y2 ? launch(SaShapes2{}, SaRow<2>{}, PiecesY2{}, SaRow<1>{}) : launch(SaShapes2{}, SaRow<2>{}, Pieces{}, SaRow<0>{}));
   return found ? mvp_launch_status() : MVP_EUNSUPPORTED;
+}
+
+MVP_API int mvp_sa_train_backward_f32(int layer, const float* zf, const float* xyz, const float* centre, const int64_t* index,
+                                      const float* wxyz, int64_t B, int64_t N, int64_t M, int64_t K, int64_t C1, const float* bn1_mean,
+                                      const float* bn1_invstd, const float* bn1_gamma, const float* bn1_beta, const float* W2, int64_t C2,
+                                      const float* bn2_mean, const float* bn2_invstd, const float* bn2_gamma, const float* bn2_beta,
+                                      const float* W3, int64_t C3, const float* mean_i, const float* invstd_i, const float* gamma_i,
+                                      const double* stat_i, float* dgamma_i, float* dbeta_i, int training, const float* G,
+                                      const float* pool_dout, const float* pool_out, const uint8_t* pool_arg, float* dW, int64_t lddw,
+                                      float* dZ, double* stat_prev, float* tsum, mvp_stream_t stream) {
+  return mvp_sa_train_backward_y2_f32(layer, zf, xyz, centre, index, wxyz, B, N, M, K, C1, bn1_mean, bn1_invstd, bn1_gamma, bn1_beta, W2, C2, bn2_mean,
+                                      bn2_invstd, bn2_gamma, bn2_beta, W3, C3, mean_i, invstd_i, gamma_i, stat_i, dgamma_i, dbeta_i, training, G,
+                                      pool_dout, pool_out, pool_arg, dW, lddw, dZ, stat_prev, tsum, nullptr, stream);
 }
 
 // Geometry-only sums of a level (see sa_geom_sums_kernel): from the transposed ball index (offsets (B,N+1), slots (B,M*32): mvp_csr_build_i64

@@ -1457,6 +1457,19 @@ def linear_rows_bf16(x, weight, bias=None, scale=None, shift=None, relu=False):
 # the per-point tensor zf instead of loading stored activations.  MVP_SA_TRAIN=0: the per-layer path (A/B switch).
 SA_TRAIN_FUSED = os.environ.get('MVP_SA_TRAIN', '1') != '0'
 
+# ... except y_2 where that is faster: forward pass 2 then stores it once and the passes named here read it instead of re-creating it
+# ('fwd3': forward pass 3, 'bwd3' / 'bwd2': the layer-3 / layer-2 backward).  By the level's block shape (c1b, c2b, c3b), 32 channels to a
+# block; a level without an entry stores nothing.  Filled in from the per-pass times in profiles/sa_y2.txt.  MVP_SA_Y2=0: re-computation
+# everywhere (A/B switch).
+SA_Y2 = os.environ.get('MVP_SA_Y2', '1') != '0'
+SA_Y2_PASSES = {(1, 1, 2): ('fwd3', 'bwd3'), (2, 2, 4): ('fwd3', 'bwd3')}   # (the layer-2 backward reads at 0.7 of the HBM peak as it is: it loses)
+
+
+def sa_y2_passes(c1, c2, c3):
+    """The passes of a (c1, c2, c3)-wide fused training level that read a stored y_2 (empty: the level stores none)."""
+    blocks = lambda c: 1 if c <= 32 else 2 if c <= 64 else 4
+    return SA_Y2_PASSES.get((blocks(c1), blocks(c2), blocks(c3)), ()) if SA_Y2 else ()
+
 
 # replicas of the per-point statistics pass' fp64 sums (the workgroups' closing atomics queue per address); MVP_SA_STATS1_REPLICAS=0: none (A/B)
 STATS1_REPLICAS = int(os.environ.get('MVP_SA_STATS1_REPLICAS', '16'))
@@ -1484,7 +1497,8 @@ class SALevelTrain(torch.autograd.Function):
     """One set-abstraction level in training mode (QueryGrouper + SharedMLP(ndim=2) + max over the neighbours: mvpnet/models/pn2/modules.py:
     20-37,100-108, conv.py:41-51 with batch statistics) WITHOUT any (B*M*32, C) activation tensor: three forward passes (statistics of
     y_1; of y_2; of y_3 + per-ball max / min) and three backward passes (layer 3; layer 2; per point through the transposed index) that
-    each re-create the ball's rows from zf, the coordinates and the ball index (csrc/sa_train.hip).  Only dz_2 and dz_1 are stored.
+    each re-create the ball's rows from zf, the coordinates and the ball index (csrc/sa_train.hip).  Only dz_2 and dz_1 are stored --
+    and y_2 on the levels of SA_Y2_PASSES, from forward pass 2 to the layer-2 backward, for the passes that read it there.
     Gradients: zf, the first layer's coordinate columns (into the weight's gradient sink), W2, W3, the three BatchNorms' parameters."""
 
     @staticmethod
@@ -1517,9 +1531,11 @@ class SALevelTrain(torch.autograd.Function):
         L.call('mvp_sa_train_stats1_ws_f32', zf, L.ptr(zf), L.ptr(dsum), L.ptr(wxyz), L.ptr(gsum), B, N, M, K, C1, L.ptr(stat1), L.ptr(zsum), float(e1),
                float(mo1), L.ptr(m1), L.ptr(i1), L.ptr(rm1), L.ptr(rv1), L.ptr(nb1), L.ptr(rep1) if nrep else None, rep1.numel())
         level = (L.ptr(zf), L.ptr(xyz), L.ptr(centre), L.ptr(index), L.ptr(wxyz), B, N, M, K, C1, L.ptr(m1), L.ptr(i1), L.ptr(g1), L.ptr(b1), L.ptr(W2), C2)
-        # pass 2: statistics of y_2
+        # pass 2: statistics of y_2 (and y_2 itself where a later pass reads it)
+        loads = sa_y2_passes(C1, C2, C3)
+        y2 = torch.empty((B * M * K, C2), dtype=torch.float32, device=dev) if loads else None
         L.call('mvp_sa_train_forward_f32', xyz, 2, *level, None, None, None, None, None, 0, L.ptr(stat2), float(e2), float(mo2), L.ptr(m2), L.ptr(i2),
-               L.ptr(rm2), L.ptr(rv2), L.ptr(nb2), None, None, None, None, prec=prec)
+               L.ptr(rm2), L.ptr(rv2), L.ptr(nb2), None, None, None, None, prec=prec, y2=L.ptr(y2))
         # pass 3: statistics of y_3 + per ball max / min of the pre-BN values
         G = B * M
         ymax = torch.empty((G, C3), dtype=torch.float32, device=dev)
@@ -1527,7 +1543,8 @@ class SALevelTrain(torch.autograd.Function):
         amax = torch.empty((G, C3), dtype=torch.uint8, device=dev)
         amin = torch.empty((G, C3), dtype=torch.uint8, device=dev)
         L.call('mvp_sa_train_forward_f32', xyz, 3, *level, L.ptr(m2), L.ptr(i2), L.ptr(g2), L.ptr(b2), L.ptr(W3), C3, L.ptr(stat3), float(e3), float(mo3),
-               L.ptr(m3), L.ptr(i3), L.ptr(rm3), L.ptr(rv3), L.ptr(nb3), L.ptr(ymax), L.ptr(ymin), L.ptr(amax), L.ptr(amin), prec=prec)
+               L.ptr(m3), L.ptr(i3), L.ptr(rm3), L.ptr(rv3), L.ptr(nb3), L.ptr(ymax), L.ptr(ymin), L.ptr(amax), L.ptr(amin), prec=prec,
+               y2=L.ptr(y2) if 'fwd3' in loads else None)
         out = torch.empty((G, C3), dtype=torch.float32, device=dev)
         arg = torch.empty((G, C3), dtype=torch.uint8, device=dev)
         ysel = torch.empty((G, C3), dtype=torch.float32, device=dev)
@@ -1535,6 +1552,9 @@ class SALevelTrain(torch.autograd.Function):
                L.ptr(out), L.ptr(arg), L.ptr(ysel))
         ctx.save_for_backward(zf, xyz, centre, index, offsets, slots, dsum, gsum, zsum, wxyz, mi, g1, b1, g2, b2, g3, W2, W3, out, arg, ysel)
         ctx.dims = (B, N, M, K, C1, C2, C3)
+        # (not among the saved tensors: the backward drops it behind its last reader, and a second backward of a retained graph re-computes)
+        ctx.y2 = y2 if 'bwd3' in loads or 'bwd2' in loads else None
+        ctx.y2_loads = loads
         return out.view(B, M, C3)
 
     @staticmethod
@@ -1562,13 +1582,18 @@ class SALevelTrain(torch.autograd.Function):
         dg3, db3 = dgb[2 * (C1 + C2):2 * (C1 + C2) + C3], dgb[2 * (C1 + C2) + C3:]
         level = (L.ptr(zf), L.ptr(xyz), L.ptr(centre), L.ptr(index), L.ptr(wxyz), B, N, M, K, C1, L.ptr(m1), L.ptr(i1), L.ptr(g1), L.ptr(b1), L.ptr(W2), C2,
                  L.ptr(m2), L.ptr(i2), L.ptr(g2), L.ptr(b2))
+        y2, ctx.y2 = ctx.y2, None
         dz2 = torch.empty((R, C2), dtype=torch.float32, device=dev)
         L.call('mvp_sa_train_backward_f32', zf, 3, *level, L.ptr(W3), C3, L.ptr(m3), L.ptr(i3), L.ptr(g3), L.ptr(stat3), L.ptr(dg3), L.ptr(db3), 1, None,
-               L.ptr(g), L.ptr(out), L.ptr(arg), L.ptr(dW3), C2, L.ptr(dz2), L.ptr(stat2), None, prec=prec)
+               L.ptr(g), L.ptr(out), L.ptr(arg), L.ptr(dW3), C2, L.ptr(dz2), L.ptr(stat2), None, prec=prec,
+               y2=L.ptr(y2) if 'bwd3' in ctx.y2_loads else None)
+        if 'bwd2' not in ctx.y2_loads:
+            y2 = None   # (dropped behind its last reader)
         dz1 = torch.empty((R, C1), dtype=torch.float32, device=dev)
         L.call('mvp_sa_train_backward_f32', zf, 2, *level, None, 0, L.ptr(m2), L.ptr(i2), L.ptr(g2), L.ptr(stat2), L.ptr(dg2), L.ptr(db2), 1, L.ptr(dz2),
-               None, None, None, L.ptr(dW2), C1, L.ptr(dz1), L.ptr(stat1), L.ptr(tsum), prec=prec)
-        del dz2
+               None, None, None, L.ptr(dW2), C1, L.ptr(dz1), L.ptr(stat1), L.ptr(tsum), prec=prec,
+               y2=L.ptr(y2) if 'bwd2' in ctx.y2_loads else None)
+        del dz2, y2
         # pass 1: per point through the transposed index; the coordinate columns' gradient goes straight into the weight's full-size gradient
         numel = 1
         for d in ctx.w_shape:
