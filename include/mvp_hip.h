@@ -1114,6 +1114,32 @@ int mvp_vote_gather_f32(const float* logit, int64_t ld_chunk, int64_t ld_r, int6
                         mvp_stream_t stream);
 int mvp_vote_finish_f32(const float* sum, const int32_t* count, int64_t n_pts, int64_t C, float* mean, int64_t* label,
                         mvp_stream_t stream);
+/* the whole-scene test of the 2D baseline behind the 2D network (mvpnet/test_2d_chunks.py:119-157 with mvpnet/models/mvpnet_2d.py:22-34:
+ * per chunk, class logits gathered through the pixel k-NN, averaged over k, `+=` into the scene) in ONE launch, atomics-free, from a
+ * store that holds the logits of every DISTINCT picked frame once.
+ *   logit: element (store frame u, pixel q, class c) at logit[u*ld_f + q*ld_p + c*ld_c], U frames of hw = h*w pixels and C classes: the
+ *     network's output where it lies, NCHW (ld_c = hw, ld_p = 1) or channels-last (ld_p = C, ld_c = 1).  A channels-last store with
+ *     C % 4 == 0, ld_p % 4 == 0, ld_f % 4 == 0 and 16-byte aligned logit / sum is read with 16-byte loads; anything else one dword per class.
+ *   view_frame (num_chunks,nv) int32: the store frame of each chunk's view; a frame outside [0,U) counts as missing.
+ *   knn: int64 rows of k chunk-local flat pixel ids view*hw + q, as mvp_lift_f32 / mvp_pixel_knn_projective_f32 write them; an id < 0
+ *     (or >= nv*hw) is missing.  knn_base (num_chunks) int64: the row in knn of each chunk's first point (chunks are searched in padded
+ *     batches, so their rows are not back to back).  Rows beyond a chunk's valid length are never read.
+ *   chunk_offsets (num_chunks + 1), point_offsets (n_pts + 1), point_slots: exactly as mvp_vote_gather_f32 takes them.
+ *   sum (n_pts,C), count (n_pts): WRITTEN, not accumulated.
+ * Definition (pinned).  For position e of the concatenated chunk lists, in chunk i at row r = e - chunk_offsets[i], with l_j[c] the
+ * logit of neighbour j = knn[(knn_base[i] + r)*k + j] -- +0 for a missing one --:
+ *     m_e[c] = (((l_0[c] + l_1[c]) + ...) + l_{k-1}[c]) / k     in float32, every addition and the division rounded once (__fdiv_rn,
+ *                                                               no reciprocal), never contracted;
+ *     sum[p][c] = ((0 + m_e1[c]) + m_e2[c]) + ...               over p's positions in ASCENDING position = chunk order, the reference's
+ *                                                               `+=` order; count[p] = the number of positions.
+ * The same bits every run.  Mean and labels: mvp_vote_finish_f32.
+ * Before any launch: MVP_EINVAL unless 1 <= k <= 8, 1 <= C <= 64, nv, U, hw, num_chunks >= 1, n_pts >= 0 and ld_f, ld_p, ld_c >= 0;
+ * MVP_EUNSUPPORTED unless nv*hw < 2^31, U < 2^31, num_chunks < 2^30, num_chunks*nv < 2^31 and n_pts < 2^31 (what the kernel holds in 32
+ * bits; offsets into logit, knn and sum are formed in 64).  n_pts == 0: nothing is launched. */
+int mvp_lift_vote_f32(const float* logit, int64_t ld_f, int64_t ld_p, int64_t ld_c, int64_t U, int64_t hw, int64_t C,
+                      const int32_t* view_frame, int64_t nv, const int64_t* knn, int64_t k, const int64_t* knn_base,
+                      const int64_t* chunk_offsets, int64_t num_chunks, const int32_t* point_offsets, const int32_t* point_slots,
+                      int64_t n_pts, float* sum, int32_t* count, mvp_stream_t stream);
 /* whole-scene voting (mvpnet/test_3d_scene.py:152-164: per vote a scikit-learn ball tree over the vote's sampled points on the host,
  * `pred_logit_whole_scene += seg_logit_per_vote[nn_indices[:, 0]]`): all votes in ONE query launch behind one grid-build launch.
  * points (n,3): the scene's points, shared by all votes.  key (V,nb,3): the sampled points of each vote.  logit: element (v,j,c) at

@@ -8,7 +8,7 @@ from .knn_distance import knn_distance
 from .interpolate import feature_interpolate
 from .lifting import unproject, pixel_knn, lift_gather, lift, rotate_rows
 from .overlap import rgbd_overlap, select_frames_batched, pack_bits, unpack_bits
-from .vote import vote_nearest
+from .vote import vote_nearest, lift_vote
 from .sample import sample_chunks
 from .scene_sample import sample_scenes, gather_cloud
 from .chunker import scene_chunks, pack_chunks
@@ -17,7 +17,7 @@ from .resize import resize_frames, prepare_labels
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
            'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
-           'pack_bits', 'unpack_bits', 'vote_nearest', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
+           'pack_bits', 'unpack_bits', 'vote_nearest', 'lift_vote', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
            'prepare_frames', 'resize_frames', 'prepare_labels']
 
 

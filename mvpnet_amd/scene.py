@@ -212,6 +212,15 @@ def _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, who, k, ima
     """-> batch(sel, points, pixel_box): one batch of a scene, the frames `sel` (B,nv) beside the chunks' points (B,3,N) and pixel boxes (B,4).
     The frames come from the lifting-resolution depth maps and the intrinsics scaled to them with their inverse (scannet_2d3d.py:206-210,
     :38), per frame, on the device."""
+    ldepth, cam, kinv = _scene_cameras(dev, depth, cam_matrix, images, lift_depth, who, image_normalizer, channels_last)
+    return lambda sel, points, pixel_box: {**_picked_views(images, ldepth, pose, sel, image_normalizer, channels_last), 'points': points,
+                                           'cam_matrix': cam[sel].contiguous(), 'kinv': kinv[sel].contiguous(),
+                                           'pixel_box': pixel_box.contiguous(), 'k': int(k)}
+
+
+def _scene_cameras(dev, depth, cam_matrix, images, lift_depth, who, image_normalizer=None, channels_last=False):
+    """-> (the lifting-resolution depth maps (F,H,W), cam (F,3,3), kinv (F,3,3)): the intrinsics scaled to those maps and their inverse
+    (scannet_2d3d.py:206-210, :38), per frame, on the device; `who` refuses images that disagree with the maps."""
     import numpy as np
     ldepth = depth if lift_depth is None else lift_depth
     F, H, W = ldepth.shape
@@ -222,10 +231,7 @@ def _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, who, k, ima
     cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
     cam[..., 1, :] /= np.float32(depth.size(1) / H)
     kinv = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(cam))).to(dev).expand(F, 3, 3)  # float32, :38
-    cam = torch.from_numpy(cam).to(dev).expand(F, 3, 3)
-    return lambda sel, points, pixel_box: {**_picked_views(images, ldepth, pose, sel, image_normalizer, channels_last), 'points': points,
-                                           'cam_matrix': cam[sel].contiguous(), 'kinv': kinv[sel].contiguous(),
-                                           'pixel_box': pixel_box.contiguous(), 'k': int(k)}
+    return ldepth, torch.from_numpy(cam).to(dev).expand(F, 3, 3), kinv
 
 
 def _raw_frames(who, images, **given):
@@ -326,6 +332,122 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
         lo = hi
     chunk_inds = torch.split(csr['index'], lengths)
     return chunk_batches, [chunk_inds[c] for c in order], n_pts, order
+
+
+def infer_scene_2d(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
+                   overlap=None, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None, image_normalizer=None, channels_last=False,
+                   frame_batch=32):
+    """The whole-scene test of the 2D baseline (mvpnet/test_2d_chunks.py:119-157) from a scene's raw arrays: the 2D network's per-pixel
+    class logits lifted to every chunk's points through the pixel k-NN, averaged over k and voted into the scene.  Single process.
+    model: an MVPNet2D, or anything with a `.net_2d` that maps {'image' (F,3,H,W)} to {'seg_logit' (F,C,H,W)}; run in eval mode under
+    no_grad, its mode is restored.  The other arguments are prepare_scene's (raw (F,H,W,3) uint8 frames with `image_normalizer` /
+    `channels_last` included); frame_batch: frames per forward of the 2D network.
+
+    The reference feeds the chunks one by one, each with its own num_rgbd_frames frames, so the 2D network sees a frame once per chunk
+    that picked it.  In eval mode a frame's logits do not depend on its batch neighbours: here the network runs ONCE per distinct picked
+    frame and writes into one channels-last logit store; the pixel k-NN runs per chunk against that chunk's own views and box, in
+    size-bucketed batches (plan_buckets with min_nb_pts = 1: there is no FPS to pad for; the padded rows are searched and never read),
+    into one flat index buffer; ops.lift_vote then goes from every scene point through its chunk positions and their k pixel ids to the
+    logit rows in one launch, adding in the chunker's chunk order -- the reference's -- and mvp_vote_finish_f32 divides and labels.
+    One device-to-host read beyond _scene_chunks': the number of distinct picked frames.
+    -> mean logits (n_pts,C), labels (n_pts,) with C where no chunk holds the point, counts (n_pts,) int32.  A scene with no kept window
+    gives zeros, labels all C and counts zero (C: net_2d.num_classes, else one frame is run to learn it)."""
+    from . import _lib as L
+    dev, n_pts = points.device, points.size(0)
+    parts = _scene_2d_inputs(model, points, depth, cam_matrix, pose, images, chunk_size=chunk_size, chunk_stride=chunk_stride, chunk_thresh=chunk_thresh,
+                             chunk_margin=chunk_margin, num_rgbd_frames=num_rgbd_frames, k=k, overlap=overlap, lift_depth=lift_depth,
+                             num_base_pts=num_base_pts, radius=radius, generator=generator, image_normalizer=image_normalizer,
+                             channels_last=channels_last, frame_batch=frame_batch)
+    C = parts['num_classes']
+    if 'logit' not in parts:
+        return (torch.zeros((n_pts, C), dtype=torch.float32, device=dev), torch.full((n_pts,), C, dtype=torch.int64, device=dev),
+                torch.zeros((n_pts,), dtype=torch.int32, device=dev))
+    total, count = ops.lift_vote(parts['logit'], parts['view_frame'], parts['knn'], parts['knn_base'], parts['chunk_inds'], n_pts)
+    mean = torch.empty_like(total)
+    label = torch.empty(n_pts, dtype=torch.int64, device=dev)
+    L.call('mvp_vote_finish_f32', total, L.ptr(total), L.ptr(count), n_pts, C, L.ptr(mean), L.ptr(label))
+    return mean, label, count
+
+
+def _scene_2d_inputs(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
+                     overlap, lift_depth, num_base_pts, radius, generator, image_normalizer, channels_last, frame_batch):
+    """infer_scene_2d up to the vote: -> {'num_classes'} for a scene without a kept window, else what ops.lift_vote takes -- logit (U,C,H,W)
+    in channels-last memory: the store of the distinct picked frames' logits; view_frame (num_chunks,nv) int32; knn (R,k) int64 and
+    knn_base: the chunks' rows, batch after batch; chunk_inds in the chunker's order -- and picked (num_chunks,nv)."""
+    from . import _lib as L
+    dev, nv, k = points.device, int(num_rgbd_frames), int(k)
+    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32 or not points.is_cuda:
+        raise RuntimeError('infer_scene_2d: points must be (n,3) float32 on the device')
+    if not 1 <= k <= ops.vote.MAX_K or frame_batch < 1:
+        raise RuntimeError('infer_scene_2d: needs 1 <= k <= {} and frame_batch >= 1'.format(ops.vote.MAX_K))
+    ldepth, cam, kinv = _scene_cameras(dev, depth, cam_matrix, images, lift_depth, 'infer_scene_2d', image_normalizer, channels_last)
+    F, H, W = ldepth.shape
+    net = model.module if hasattr(model, 'module') else model
+    net_2d = net.net_2d
+
+    def run_2d(frames):  # (b,) int64 on the device -> (b,C,H,W)
+        if images.dtype == torch.uint8:
+            x = ops.prepare_frames(images, frames, normalizer=image_normalizer, channels_last=channels_last)
+        else:
+            x = images[frames].contiguous()
+        return net_2d({'image': x})['seg_logit']
+
+    csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
+                        num_base_pts, radius, generator)
+    lengths = csr['lengths']
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            if not lengths:
+                C = getattr(net_2d, 'num_classes', None)
+                C = int(run_2d(torch.zeros(1, dtype=torch.int64, device=dev)).size(1)) if C is None else int(C)
+                return {'num_classes': C}
+            if min(lengths) < 1:
+                raise RuntimeError('infer_scene_2d: a chunk without points (chunk_thresh must be at least 1)')
+            # the distinct picked frames, ascending, and every view's place among them
+            picked = csr['picked']  # (num_chunks,nv) int64
+            present = torch.zeros(F, dtype=torch.bool, device=dev)
+            present[picked.reshape(-1)] = True
+            slot = torch.cumsum(present, 0) - 1
+            view_frame = slot[picked].to(torch.int32)
+            U = int(present.sum())  # (the one read)
+            distinct = torch.sort((~present).to(torch.uint8), stable=True).indices[:U]
+            store = None
+            for lo in range(0, U, int(frame_batch)):
+                out = run_2d(distinct[lo:lo + int(frame_batch)])
+                if store is None:
+                    if out.dim() != 4 or tuple(out.shape[2:]) != (H, W) or out.dtype != torch.float32:
+                        raise RuntimeError('infer_scene_2d: net_2d must return float32 seg_logit (F,C,{},{}), the lifting maps\' size'.format(H, W))
+                    # channels-last memory whatever the network writes: the copy into the store is needed anyway, and it makes a
+                    # neighbour's C logits one contiguous row
+                    store = torch.empty((U, H, W, out.size(1)), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+                store[lo:lo + out.size(0)].copy_(out)
+            # pixel k-NN per chunk, in size-bucketed batches, into one flat buffer
+            batches, _ = plan_buckets(lengths, min_nb_pts=1)
+            out_base, out_len, knn_base, at, rows = [0] * len(lengths), [0] * len(lengths), [0] * len(lengths), 0, 0
+            for N, members in batches:
+                for c in members:
+                    out_base[c], out_len[c], knn_base[c], at, rows = at, N, rows, at + 3 * N, rows + N
+            packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len)
+            knn = torch.empty((rows, k), dtype=torch.int64, device=dev)
+            order_t = torch.tensor([c for _, members in batches for c in members], dtype=torch.int64).to(dev)
+            sel_all, box_all = picked[order_t], csr['pixel_box'][order_t]
+            pose, lo = pose.contiguous(), 0
+            for N, members in batches:
+                B, first = len(members), out_base[members[0]]
+                sel = sel_all[lo:lo + B]
+                pts = packed[first:first + B * 3 * N].view(B, 3, N).transpose(1, 2).contiguous()
+                bcam, bpose = cam[sel].contiguous(), pose[sel].contiguous()
+                xyz, mask = ops.unproject(ldepth[sel].contiguous(), kinv[sel].contiguous(), bpose, box_all[lo:lo + B].contiguous())
+                mask = mask.to(torch.uint8)
+                L.call('mvp_pixel_knn_projective_f32', pts, L.ptr(xyz), L.ptr(mask), L.ptr(pts), L.ptr(bcam), L.ptr(bpose), B, nv, H, W, N, k,
+                       L.ptr_at(knn, knn_base[members[0]] * k), None)
+                lo += B
+            return {'logit': store, 'view_frame': view_frame, 'knn': knn, 'knn_base': knn_base, 'chunk_inds': list(torch.split(csr['index'], lengths)),
+                    'picked': picked, 'num_classes': int(store.size(1))}
+    finally:
+        model.train(was_training)
 
 
 def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2), chunk_thresh=0.3,
