@@ -280,6 +280,19 @@ int mvp_lift_aug_f32(const void* depth, int depth_is_u16, const float* kinv, con
                      int64_t w, int64_t N, int64_t C, int64_t k, void* workspace, int64_t* knn_index, float* gfeature,
                      float* gxyz, float* image_xyz, uint8_t* mask, const uint8_t* flip, const double* rot, float* points_out,
                      mvp_stream_t stream);
+/* mvp_lift_f32 with the feature rows read from a store shared by all chunks (whole-scene test: every distinct frame goes through the
+ * 2D network once, scene.infer_scene_shared) instead of a per-batch (B,nv,h,w,C) tensor.  Forward only; no flip, no rotation.
+ *   store (U,h,w,C) float32 channels-last, 16-byte aligned: one feature map per distinct frame, U * h * w < 2^31 (else
+ *        MVP_EUNSUPPORTED); view_slot (B,nv) int32: the store slot of view v of chunk b;
+ *   depth, kinv, cam, pose, box, points, workspace (mvp_lift_workspace_bytes), the shape limits: as mvp_lift_f32
+ *   -> knn_index (B,N,k) int64: the chunk-local flat ids view*h*w + pixel, what mvp_lift_f32 writes; gfeature (B,N,k,C) (required):
+ *      neighbour id = v*h*w + p of chunk b is row view_slot[b,v]*h*w + p of the store -- a slot outside [0,U) counts as a missing
+ *      neighbour: a zero row, never an address (the convention of mvp_lift_vote_f32) --; gxyz (B,N,k,3) or NULL.
+ *   Bit-equal to mvp_lift_f32 on the materialised copy store[view_slot]. */
+int mvp_lift_store_f32(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                       const float* box, const float* points, const float* store, const int32_t* view_slot, int64_t U,
+                       int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace,
+                       int64_t* knn_index, float* gfeature, float* gxyz, mvp_stream_t stream);
 /* out[b,r,:] = float32( rot[b] (float64 3x3) . xyz[b,r,:] ), rows R per batch element: the z-rotation augmentation of `points`
  * / `image_xyz` (scannet_2d3d.py:400-409) for tensors that did not go through mvp_lift_aug_f32.  In place allowed. */
 int mvp_rotate_rows_f32(const float* xyz, const double* rot, int64_t B, int64_t R, float* out, mvp_stream_t stream);

@@ -68,6 +68,8 @@ _SIGNATURES = {
                      _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     'mvp_lift_aug_f32': [_ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr,
                          _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    'mvp_lift_store_f32': [_ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr,
+                           _ptr, _ptr, _ptr, _ptr],
     'mvp_rotate_rows_f32': [_ptr, _ptr, _i64, _i64, _ptr, _ptr],
     'mvp_copy_slices_f32': [_ptr, _i64, _ptr],
     'mvp_group_rows_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],

@@ -8,6 +8,8 @@
 //                                 (pixel_knn_core.h); the workgroup then gathers the k x 256 neighbour rows of the channels-last
 //                                 feature map (16 lanes x 16 B per 256-byte row, full-line loads, non-temporal full-line stores)
 //                                 and the neighbours' xyz.
+//   K2' lift_knn_gather_store_kernel : K2 for the whole-scene test path (mvp_lift_store_f32): the rows come from one feature store shared
+//                                 by all chunks through a (B,nv) slot table; same search, same gather loop.
 //
 // Replaces, on the device, scannet_2d3d.py:254-313 (loader workers) + mvpnet_3d.py:99-109 (two channel-major group_points
 // calls and a full transpose copy).  Measurements, ablations and the alternatives that were built and dropped: DESIGN.md 4.1.
@@ -480,6 +482,45 @@ __device__ __forceinline__ void filtered_search(const float4* __restrict__ crec,
 __device__ unsigned long long g_lift_ts[4 * 8192];  // per workgroup: start, search done, gather done (100 MHz real-time clock)
 #endif
 
+// The gather of one workgroup: `rows` (= its points x K) rows of C floats, contiguous in the output; sidx[r] = the row of `fb` that output
+// row r copies, negative = a zero row.  16 lanes x 16 B per 256-byte row (C = 64), MVP_GATHER_U rows in flight per lane.
+#ifndef MVP_GATHER_U
+#define MVP_GATHER_U 8
+#endif
+template <int K, int T>
+__device__ __forceinline__ void gather_rows(const float4* fb, float4* ob, const int* sidx, int rows, int C, int tid) {
+  const int C4 = C >> 2;               // C % 4 == 0 checked by the host entry
+  const int rpp = T / C4;     // rows per pass (16 for C = 64 and 256 threads)
+  const int c4 = tid % C4, r0 = tid / C4;
+  // Output rows are written once and never re-read by this kernel: non-temporal stores keep them
+  // from displacing the records / feature rows in L2 (measured 70 -> 57 us on the gather alone).
+  constexpr int U = MVP_GATHER_U;  // rows in flight per lane
+  for (int r = r0; r < rows; r += rpp * U) {
+    float4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u * rpp;
+      v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (rr < rows) {
+        const int id = sidx[rr];
+        if (id >= 0) v[u] = fb[(size_t)id * C4 + c4];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u * rpp;
+      if (rr < rows) {
+        float4* dst = ob + (size_t)rr * C4 + c4;
+#ifdef MVP_GATHER_PLAIN_STORE
+        *dst = v[u];
+#else
+        __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(&v[u]), reinterpret_cast<f32x4*>(dst));
+#endif
+      }
+    }
+  }
+}
+
 #ifndef MVP_LIFT_WAVES
 #define MVP_LIFT_WAVES 1
 #endif
@@ -588,47 +629,118 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MVP_LIFT_WAVE
 #ifdef MVP_LIFT_EXP
   if (tid == 0 && L < 8192) g_lift_ts[4 * L + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
-  // ---- gather: rows (n0 .. n0+255) x K of C floats, contiguous in the output ----
-  const int rows = min(T, N - blk * T) * K;
-  const int C4 = C >> 2;               // C % 4 == 0 checked by the host entry
-  const int rpp = T / C4;     // rows per pass (16 for C = 64 and 256 threads)
-  const int c4 = tid % C4, r0 = tid / C4;
-  const float4* fb = reinterpret_cast<const float4*>(feature + (size_t)b * P * C);
-  float4* ob = reinterpret_cast<float4*>(gfeat + ((size_t)b * N + (size_t)blk * T) * K * C);
-  // Output rows are written once and never re-read by this kernel: non-temporal stores keep them
-  // from displacing the records / feature rows in L2 (measured 70 -> 57 us on the gather alone).
-#ifndef MVP_GATHER_U
-#define MVP_GATHER_U 8
-#endif
-  constexpr int U = MVP_GATHER_U;  // rows in flight per lane
-  for (int r = r0; r < rows; r += rpp * U) {
-    float4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int rr = r + u * rpp;
-      v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (rr < rows) {
-        const int id = sidx[rr];
-        if (id >= 0) v[u] = fb[(size_t)id * C4 + c4];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int rr = r + u * rpp;
-      if (rr < rows) {
-        float4* dst = ob + (size_t)rr * C4 + c4;
-#ifdef MVP_GATHER_PLAIN_STORE
-        *dst = v[u];
-#else
-        __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(&v[u]), reinterpret_cast<f32x4*>(dst));
-#endif
-      }
-    }
-  }
+  gather_rows<K, T>(reinterpret_cast<const float4*>(feature + (size_t)b * P * C),
+                    reinterpret_cast<float4*>(gfeat + ((size_t)b * N + (size_t)blk * T) * K * C), sidx, min(T, N - blk * T) * K, C, tid);
 #ifdef MVP_LIFT_EXP
   __syncthreads();
   if (tid == 0 && L < 8192) g_lift_ts[4 * L + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
+}
+
+// lift_knn_gather_kernel for the whole-scene test path: the feature rows come from ONE store (U,h,w,C) shared by all chunks -- one map per
+// distinct frame -- through view_slot (B,nv): neighbour id = v * hw + p of chunk b is row view_slot[b,v] * hw + p of the store.  Same
+// placement, same search (filtered_search), same gather loop; the table sits in LDS beside vp[] and the store row is resolved ONCE per
+// winner, where sidx is written, so the gather loop is the one above.  A slot outside [0,U) is a missing neighbour: a zero row, never an
+// address (mvp_lift_vote_f32's convention).  knn_index keeps the chunk-local ids.  No flip, no rotation: under no_grad, un-augmented.
+// A __global__ of its own: the instances above keep their names and their code.
+template <int K, int T>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MVP_LIFT_WAVES))) void lift_knn_gather_store_kernel(
+    const float4* __restrict__ rec, const uint16_t* __restrict__ plane, int pitch, const float* __restrict__ points, const float* __restrict__ cam,
+    const float* __restrict__ pose, const float* __restrict__ store, const int* __restrict__ view_slot, int U, int B, int nv, int h, int w, int N,
+    int C, int bpc, int64_t* __restrict__ knn_index, float* __restrict__ gfeat, float* __restrict__ gxyz) {
+  __shared__ ViewParam vp[kMaxViews];
+  __shared__ int vslot[kMaxViews];
+  __shared__ int sidx[T * K];
+  __shared__ int slist[T * kSurvCap];
+  const int L = blockIdx.x;  // XCD-aware chunk placement, as above
+  int b, blk;
+  if (B >= kXcds) {
+    const int xcd = L % kXcds, jb = L / kXcds;
+    b = xcd + kXcds * (jb / bpc);
+    blk = jb % bpc;
+  } else {
+    b = L / bpc;
+    blk = L - b * bpc;
+  }
+  if (b >= B) return;  // uniform per workgroup
+  const int tid = threadIdx.x;
+  if (tid < nv) {
+    vp[tid] = make_view_param(cam + ((size_t)b * nv + tid) * 9, pose + ((size_t)b * nv + tid) * 16, h, w);
+    const int slot = view_slot[(size_t)b * nv + tid];
+    vslot[tid] = (slot >= 0 && slot < U) ? slot : -1;
+  }
+  __syncthreads();
+
+  const int hw = h * w;
+  const float4* crec = rec + (size_t)b * nv * hw;
+  const int n = blk * T + tid;
+  const bool active = n < N;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) {
+    const float* q = points + ((size_t)b * N + n) * 3;
+    qx = q[0]; qy = q[1]; qz = q[2];
+  }
+  unsigned long long kk[K];
+  filtered_search<K, T>(crec, plane + (size_t)b * nv * plane_rows(h) * pitch, vp, nv, h, w, pitch, active, qx, qy, qz, kk, slist, tid);
+  if (active) {
+    float4 wrec[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {  // the winners' coordinates: K independent loads
+      const bool found = kk[s] != ~0ull;
+      wrec[s] = (gxyz && found) ? crec[(int)(unsigned)kk[s]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      const bool found = kk[s] != ~0ull;
+      const int id = found ? (int)(unsigned)kk[s] : -1;
+      int row = -1;  // the store row of the neighbour: U * hw < 2^31 checked by the host entry
+      if (found) {
+        const int vi = id / hw;
+        const int slot = vslot[vi];
+        row = slot >= 0 ? slot * hw + (id - vi * hw) : -1;
+      }
+      sidx[tid * K + s] = row;
+      knn_index[((size_t)b * N + n) * K + s] = (int64_t)id;
+      if (gxyz) {
+        float* o = gxyz + (((size_t)b * N + n) * K + s) * 3;
+        o[0] = wrec[s].x; o[1] = wrec[s].y; o[2] = wrec[s].z;
+      }
+    }
+  }
+  __syncthreads();
+  gather_rows<K, T>(reinterpret_cast<const float4*>(store), reinterpret_cast<float4*>(gfeat + ((size_t)b * N + (size_t)blk * T) * K * C), sidx,
+                    min(T, N - blk * T) * K, C, tid);
+}
+
+// one-wave workgroups while the launch has fewer than 4 workgroups of 256 points per CU (a few dense chunks, a single chunk's latency);
+// MVP_LIFT_WG = 64 / 256 forces one shape (A/B switch).  The gather needs T % (C / 4) == 0.
+inline bool lift_small_workgroups(int64_t B, int64_t N, int64_t C) {
+  static const int force = []() { const char* e = getenv("MVP_LIFT_WG"); return e ? atoi(e) : 0; }();
+  const bool small = force == 64 || (force != 256 && B * cdiv(N, kLFThreads) < 4 * 256);
+  return small && (C == 0 || (C % 4 == 0 && 64 % (C / 4) == 0));
+}
+inline dim3 lift_grid(int64_t B, int bpc) {
+  const int64_t groups = cdiv(B, kXcds);  // chunks per XCD (rounded up; surplus workgroups exit at once)
+  return dim3((unsigned)(B >= kXcds ? kXcds * groups * bpc : B * bpc));
+}
+
+template <int K, int T>
+int launch_lift_store_t(const float4* rec, const uint16_t* plane, int pitch, const float* points, const float* cam, const float* pose,
+                        const float* store, const int* view_slot, int64_t U, int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C,
+                        int64_t* knn_index, float* gfeat, float* gxyz, hipStream_t s) {
+  const int bpc = (int)cdiv(N, T);
+  hipLaunchKernelGGL((lift_knn_gather_store_kernel<K, T>), lift_grid(B, bpc), dim3(T), 0, s, rec, plane, pitch, points, cam, pose, store, view_slot,
+                     (int)U, (int)B, (int)nv, (int)h, (int)w, (int)N, (int)C, bpc, knn_index, gfeat, gxyz);
+  return mvp_launch_status();
+}
+
+template <int K>
+int launch_lift_store(const float4* rec, const uint16_t* plane, int pitch, const float* points, const float* cam, const float* pose,
+                      const float* store, const int* view_slot, int64_t U, int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C,
+                      int64_t* knn_index, float* gfeat, float* gxyz, hipStream_t s) {
+  if (lift_small_workgroups(B, N, C))
+    return launch_lift_store_t<K, 64>(rec, plane, pitch, points, cam, pose, store, view_slot, U, B, nv, h, w, N, C, knn_index, gfeat, gxyz, s);
+  return launch_lift_store_t<K, kLFThreads>(rec, plane, pitch, points, cam, pose, store, view_slot, U, B, nv, h, w, N, C, knn_index, gfeat, gxyz, s);
 }
 
 template <int K, int T>
@@ -636,8 +748,7 @@ int launch_lift_t(const float4* rec, const uint16_t* plane, int pitch, const flo
                   int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t* knn_index, float* gfeat,
                   float* gxyz, const uint8_t* flip, const double* rot, float* points_out, hipStream_t s) {
   const int bpc = (int)cdiv(N, T);
-  const int64_t groups = cdiv(B, kXcds);  // chunks per XCD (rounded up; surplus workgroups exit at once)
-  dim3 grid((unsigned)(B >= kXcds ? kXcds * groups * bpc : B * bpc));
+  const dim3 grid = lift_grid(B, bpc);
   int sched = 0;
 #ifdef MVP_LIFT_EXP
   if (const char* e = getenv("MVP_LIFT_SCHED")) sched = atoi(e);
@@ -651,13 +762,22 @@ template <int K>
 int launch_lift(const float4* rec, const uint16_t* plane, int pitch, const float* points, const float* cam, const float* pose, const float* feature,
                 int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t* knn_index, float* gfeat,
                 float* gxyz, const uint8_t* flip, const double* rot, float* points_out, hipStream_t s) {
-  // one-wave workgroups while the launch has fewer than 4 workgroups of 256 points per CU (a few dense chunks, a single chunk's latency);
-  // MVP_LIFT_WG = 64 / 256 forces one shape (A/B switch).  The gather needs T % (C / 4) == 0.
-  static const int force = []() { const char* e = getenv("MVP_LIFT_WG"); return e ? atoi(e) : 0; }();
-  const bool small = force == 64 || (force != 256 && B * cdiv(N, kLFThreads) < 4 * 256);
-  if (small && (C == 0 || (C % 4 == 0 && 64 % (C / 4) == 0)))
+  if (lift_small_workgroups(B, N, C))
     return launch_lift_t<K, 64>(rec, plane, pitch, points, cam, pose, feature, B, nv, h, w, N, C, knn_index, gfeat, gxyz, flip, rot, points_out, s);
   return launch_lift_t<K, kLFThreads>(rec, plane, pitch, points, cam, pose, feature, B, nv, h, w, N, C, knn_index, gfeat, gxyz, flip, rot, points_out, s);
+}
+
+// K1 of every lifting entry: the search records and the depth plane of all B * nv views.
+int launch_lift_prepare(const void* depth, int depth_is_u16, const float* kinv, const float* pose, const float* box, int64_t B, int64_t nv, int64_t h,
+                        int64_t w, int pitch, float4* rec, uint16_t* plane, float* image_xyz, uint8_t* mask, const uint8_t* flip, hipStream_t s) {
+  dim3 grid((unsigned)cdiv((int64_t)plane_rows((int)h) * pitch, kPrepThreads), (unsigned)(B * nv));
+  if (depth_is_u16)
+    hipLaunchKernelGGL((lift_prepare_kernel<uint16_t>), grid, dim3(kPrepThreads), 0, s, static_cast<const uint16_t*>(depth), kinv,
+                       pose, box, (int)B, (int)nv, (int)h, (int)w, pitch, rec, plane, image_xyz, mask, flip);
+  else
+    hipLaunchKernelGGL((lift_prepare_kernel<float>), grid, dim3(kPrepThreads), 0, s, static_cast<const float*>(depth), kinv, pose,
+                       box, (int)B, (int)nv, (int)h, (int)w, pitch, rec, plane, image_xyz, mask, flip);
+  return mvp_launch_status();
 }
 
 }  // namespace
@@ -709,14 +829,7 @@ MVP_API int mvp_lift_aug_f32(const void* depth, int depth_is_u16, const float* k
   float4* rec = static_cast<float4*>(workspace);
   uint16_t* plane = reinterpret_cast<uint16_t*>(rec + B * nv * h * w);
   const int pitch = plane_pitch((int)w);
-  dim3 grid((unsigned)cdiv((int64_t)plane_rows((int)h) * pitch, kPrepThreads), (unsigned)(B * nv));
-  if (depth_is_u16)
-    hipLaunchKernelGGL((lift_prepare_kernel<uint16_t>), grid, dim3(kPrepThreads), 0, s, static_cast<const uint16_t*>(depth), kinv,
-                       pose, box, (int)B, (int)nv, (int)h, (int)w, pitch, rec, plane, image_xyz, mask, flip);
-  else
-    hipLaunchKernelGGL((lift_prepare_kernel<float>), grid, dim3(kPrepThreads), 0, s, static_cast<const float*>(depth), kinv, pose,
-                       box, (int)B, (int)nv, (int)h, (int)w, pitch, rec, plane, image_xyz, mask, flip);
-  int rc = mvp_launch_status();
+  int rc = launch_lift_prepare(depth, depth_is_u16, kinv, pose, box, B, nv, h, w, pitch, rec, plane, image_xyz, mask, flip, s);
   if (rc != MVP_OK || N == 0) return rc;
   switch (k) {
 #define MVP_CASE(KK) \
@@ -735,4 +848,42 @@ MVP_API int mvp_lift_f32(const void* depth, int depth_is_u16, const float* kinv,
                          float* gfeature, float* gxyz, float* image_xyz, uint8_t* mask, mvp_stream_t stream) {
   return mvp_lift_aug_f32(depth, depth_is_u16, kinv, cam, pose, box, points, feature, B, nv, h, w, N, C, k, workspace, knn_index,
                           gfeature, gxyz, image_xyz, mask, nullptr, nullptr, nullptr, stream);
+}
+
+// mvp_lift_f32 reading the feature rows from a store shared by all chunks (the whole-scene test path: every distinct frame goes through
+// the 2D network once).  Forward only; no flip, no rotation.
+MVP_API int mvp_lift_store_f32(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                               const float* box, const float* points, const float* store, const int32_t* view_slot, int64_t U,
+                               int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace,
+                               int64_t* knn_index, float* gfeature, float* gxyz, mvp_stream_t stream) {
+  MVP_NONNULL(depth);
+  MVP_NONNULL(kinv);
+  MVP_NONNULL(cam);
+  MVP_NONNULL(pose);
+  MVP_NONNULL(points);
+  MVP_NONNULL(store);
+  MVP_NONNULL(view_slot);
+  MVP_NONNULL(workspace);
+  MVP_NONNULL(knn_index);
+  MVP_NONNULL(gfeature);
+  MVP_REQUIRE(B >= 0 && N >= 0 && nv > 0 && h > 0 && w > 0 && k >= 1 && k <= 8 && U >= 1);
+  MVP_REQUIRE(nv * (h + 8) * (w + 14) < (1ll << 31) && N < (1ll << 31) && B * (nv + 1) < 65536 && nv <= kMaxViews);
+  MVP_REQUIRE(((uintptr_t)workspace % 16) == 0);
+  MVP_REQUIRE(C % 4 == 0 && C >= 4 && C <= 1024 && (kLFThreads % (C / 4)) == 0 && ((uintptr_t)store % 16) == 0 && ((uintptr_t)gfeature % 16) == 0);
+  if (U >= (1ll << 31) / (h * w) + ((1ll << 31) % (h * w) != 0)) return MVP_EUNSUPPORTED;  // store rows are 32-bit: U * h * w < 2^31
+  if (B == 0) return MVP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float4* rec = static_cast<float4*>(workspace);
+  uint16_t* plane = reinterpret_cast<uint16_t*>(rec + B * nv * h * w);
+  const int pitch = plane_pitch((int)w);
+  int rc = launch_lift_prepare(depth, depth_is_u16, kinv, pose, box, B, nv, h, w, pitch, rec, plane, nullptr, nullptr, nullptr, s);
+  if (rc != MVP_OK || N == 0) return rc;
+  switch (k) {
+#define MVP_CASE(KK) \
+  case KK:           \
+    return launch_lift_store<KK>(rec, plane, pitch, points, cam, pose, store, view_slot, U, B, nv, h, w, N, C, knn_index, gfeature, gxyz, s);
+    MVP_CASE(1) MVP_CASE(2) MVP_CASE(3) MVP_CASE(4) MVP_CASE(5) MVP_CASE(6) MVP_CASE(7) MVP_CASE(8)
+#undef MVP_CASE
+  }
+  return MVP_EUNSUPPORTED;
 }

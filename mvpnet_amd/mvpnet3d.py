@@ -135,6 +135,17 @@ class MVPNet3D(nn.Module):
                         k=int(data_batch.get('k', 3)), box=data_batch.get('pixel_box'), flip=data_batch.get('flip'),
                         rot=data_batch.get('z_rot'))
 
+    @staticmethod
+    def lift_store(data_batch):
+        """`lift` for a batch that carries feature_store (U,h,w,C) and view_slot (B,nv) int32 in place of `images`: the rows of the
+        shared store are read through view_slot.  Test path: no flip, no z rotation."""
+        if 'flip' in data_batch or 'z_rot' in data_batch:
+            raise RuntimeError('MVPNet3D: a batch with feature_store / view_slot takes no flip / z_rot (the un-augmented test path)')
+        cam = data_batch['cam_matrix']
+        kinv = data_batch['kinv'] if 'kinv' in data_batch else torch.linalg.inv(cam)
+        return ops.lift_store(data_batch['feature_store'], data_batch['view_slot'], data_batch['depth'], kinv, cam, data_batch['pose'],
+                              points_rows(data_batch), k=int(data_batch.get('k', 3)), box=data_batch.get('pixel_box'))
+
     def _side_stream(self, device):
         if getattr(self, '_geo_stream', None) is None or self._geo_stream.device != device:
             self._geo_stream = torch.cuda.Stream(device=device)
@@ -152,6 +163,11 @@ class MVPNet3D(nn.Module):
         if plan is None and hasattr(self.net_3d, 'plan_geometry') and points.is_cuda:
             pts_rows = points_rows(data_batch, points)
             plan = self.net_3d.plan_geometry(pts_rows, stream=self._side_stream(pts_rows.device))
+        if 'feature_store' in data_batch and 'view_slot' in data_batch:
+            # whole-scene test (scene.infer_scene_shared): the 2D network already ran ONCE per distinct frame into a store shared by all
+            # chunks; no `images`, no net_2d call, no (B,nv,h,w,C) copy -- the rows are read through view_slot (mvp_lift_store_f32)
+            gfeat, gxyz = self.lift_store(data_batch)[:2]  # (B,N,k,C), (B,N,k,3)
+            return self._after_lift(data_batch, points, plan, gfeat, gxyz)
         images = data_batch['images']  # (B,nv,3,h,w)
         b, nv, _, h, w = images.shape
         # consumed exactly once (a batch dict that is reused must not feed a stale map to a later step, nor keep the tensor pinned), and only
@@ -169,6 +185,10 @@ class MVPNet3D(nn.Module):
             gfeat, gxyz = ops.lift_gather(feature_cl, data_batch['image_xyz'], data_batch['knn_indices'])
         else:  # device lifting: un-project + pixel k-NN + gather fused (mvp_lift_f32)
             gfeat, gxyz = self.lift(feature_cl, data_batch)[:2]  # (B,N,k,C), (B,N,k,3)
+        return self._after_lift(data_batch, points, plan, gfeat, gxyz)
+
+    def _after_lift(self, data_batch, points, plan, gfeat, gxyz):
+        """Everything behind the lifting: the next batch's geometry, the aggregation and the 3D network."""
         nxt = data_batch.get('prefetch_next')
         if nxt is not None:  # start the NEXT batch's FPS / ball query / 3-NN now: runs under this batch's MLPs
             prefetch_geometry(self, nxt)

@@ -6,7 +6,7 @@ from .ball_query import ball_query, ball_query_distance
 from .group_points import group_points
 from .knn_distance import knn_distance
 from .interpolate import feature_interpolate
-from .lifting import unproject, pixel_knn, lift_gather, lift, rotate_rows
+from .lifting import unproject, pixel_knn, lift_gather, lift, lift_store, rotate_rows
 from .overlap import rgbd_overlap, select_frames_batched, pack_bits, unpack_bits
 from .vote import vote_nearest, lift_vote
 from .sample import sample_chunks
@@ -16,7 +16,7 @@ from .frames import prepare_frames
 from .resize import resize_frames, prepare_labels
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
-           'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
+           'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'lift_store', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
            'pack_bits', 'unpack_bits', 'vote_nearest', 'lift_vote', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
            'prepare_frames', 'resize_frames', 'prepare_labels']
 

@@ -179,6 +179,45 @@ def lift(feature, depth, kinv, cam, pose, points, k=3, box=None, return_image_xy
                               bool(return_image_xyz), flip, rot)
 
 
+def lift_store(store, view_slot, depth, kinv, cam, pose, points, k=3, box=None):
+    """ops.lift reading the feature rows from a store shared by all chunks (mvp_lift_store_f32; scene.infer_scene_shared): no
+    (B,nv,h,w,C) tensor per batch.  store (U,h,w,C) f32 channels-last: one feature map per distinct frame; view_slot (B,nv) int32: the
+    store slot of view v of chunk b -- a slot outside [0,U) counts as a missing neighbour, its rows are zero --; the rest as ops.lift.
+    -> gathered feature (B,N,k,C), gathered xyz (B,N,k,3), knn_indices (B,N,k) (chunk-local flat ids, as ops.lift's): bit-equal to
+    ops.lift(store[view_slot.long()], ...).  Forward only: the test path, nothing here requires grad."""
+    if store.dtype != torch.float32 or points.dtype != torch.float32 or store.dim() != 4 or store.size(-1) % 4:
+        raise RuntimeError('lift_store: float32 channels-last store (U,h,w,C) with C % 4 == 0 expected')
+    if depth.dim() != 4 or tuple(store.shape[1:3]) != tuple(depth.shape[2:]):
+        raise RuntimeError('lift_store: depth must be (B,nv,h,w) at the store\'s (h,w)')
+    if view_slot.dtype != torch.int32 or tuple(view_slot.shape) != tuple(depth.shape[:2]):
+        raise RuntimeError('lift_store: view_slot must be (B,nv) int32')
+    # the small operands are made contiguous as ops.lift does; a non-contiguous STORE is refused: copying it is what this op is there to avoid
+    view_slot, depth, kinv, cam, pose, points = (t.contiguous() for t in (view_slot, depth, kinv, cam, pose, points))
+    box = None if box is None else box.contiguous()
+    L.require_gpu(store, view_slot, depth, kinv, cam, pose, box, points)
+    B, nv, h, w = depth.shape
+    N, C, k = points.size(1), store.size(-1), int(k)
+    if depth.dtype == torch.float32:
+        is_u16 = 0
+    elif depth.dtype in (torch.int16, torch.uint16):
+        is_u16 = 1
+    else:
+        raise RuntimeError('lift_store: depth must be float32 (m) or (u)int16 (mm)')
+    if kinv.dtype != torch.float32 or cam.dtype != torch.float32 or pose.dtype != torch.float32 or (box is not None and box.dtype != torch.float32):
+        raise RuntimeError('lift_store: kinv, cam, pose and box must be float32')
+    if tuple(kinv.shape) != (B, nv, 3, 3) or tuple(cam.shape) != (B, nv, 3, 3) or tuple(pose.shape) != (B, nv, 4, 4) or \
+            tuple(points.shape) != (B, N, 3) or (box is not None and tuple(box.shape) != (B, 4)):
+        raise RuntimeError('lift_store: kinv, cam (B,nv,3,3), pose (B,nv,4,4), points (B,N,3) and box (B,4) expected')
+    with torch.no_grad():
+        ws = torch.empty(L.lib().mvp_lift_workspace_bytes(B, nv, h, w, N), dtype=torch.uint8, device=depth.device)
+        knn = torch.empty((B, N, k), dtype=torch.int64, device=depth.device)
+        gfeat = torch.empty((B, N, k, C), dtype=torch.float32, device=depth.device)
+        gxyz = torch.empty((B, N, k, 3), dtype=torch.float32, device=depth.device)
+        L.call('mvp_lift_store_f32', depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points), L.ptr(store),
+               L.ptr(view_slot), store.size(0), B, nv, h, w, N, C, k, L.ptr(ws), L.ptr(knn), L.ptr(gfeat), L.ptr(gxyz))
+    return gfeat, gxyz, knn
+
+
 def rotate_rows(xyz, rot):
     """xyz (B, ..., 3) float32, rot (B,3,3) float64 -> float32( rot[b] . xyz ) per row (scannet_2d3d.py:400-409)."""
     if xyz.dtype != torch.float32 or rot.dtype != torch.float64 or xyz.size(-1) != 3 or tuple(rot.shape) != (xyz.size(0), 3, 3):

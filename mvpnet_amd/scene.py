@@ -39,13 +39,25 @@ def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_cl
     n_pts: number of scene points.
     Returns mean logits (n_pts, C), labels (n_pts,) with C = "no prediction" where a point is in no chunk, vote counts."""
     num_chunks = len(chunk_inds) if num_chunks is None else num_chunks
-    outs = []
     was_training = model.training
     model.eval()
     net = model.module if hasattr(model, 'module') else model
     net3d = getattr(net, 'net_3d', net)
     if num_classes is None:
         num_classes = int(net3d.num_classes)
+    outs = _forward_batches(model, chunk_batches)
+    model.train(was_training)
+    return _vote_chunk_logits(outs, chunk_inds, n_pts, num_chunks, num_classes)
+
+
+def _forward_batches(model, chunk_batches, ready=None):
+    """infer_scene's loop: the batches through `model` (in eval mode already) under no_grad, the coordinate-only work planned ahead on the
+    side stream -> the batches' seg_logit.  ready(i, batch) -> the dict batch i is fed as, called right before its forward (infer_scene_shared
+    hangs the run's feature store in there); the planning reads `points` only, so it never waits for it."""
+    ready = ready or (lambda i, b: b)
+    outs = []
+    net = model.module if hasattr(model, 'module') else model
+    net3d = getattr(net, 'net_3d', net)
     clouds = sum(b['points'].size(0) for b in chunk_batches)
     same_n = len({b['points'].size(2) for b in chunk_batches}) <= 1
     with torch.no_grad():
@@ -57,17 +69,22 @@ def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_cl
             side = net._side_stream(pts.device) if hasattr(net, '_side_stream') else torch.cuda.Stream(device=pts.device)
             plan = net3d.plan_geometry(pts, stream=side, with_csr=False)
             lo = 0
-            for b in chunk_batches:
+            for i, b in enumerate(chunk_batches):
                 hi = lo + b['points'].size(0)
-                outs.append(model(dict(b, geometry_plan=net3d.slice_plan(plan, lo, hi)))['seg_logit'])
+                outs.append(model(dict(ready(i, b), geometry_plan=net3d.slice_plan(plan, lo, hi)))['seg_logit'])
                 lo = hi
         else:
             cur = prefetch_geometry(model, dict(chunk_batches[0])) if chunk_batches else None
             for i in range(len(chunk_batches)):
                 nxt = dict(chunk_batches[i + 1]) if i + 1 < len(chunk_batches) else None
+                cur = ready(i, cur)
                 outs.append(model(cur if nxt is None else dict(cur, prefetch_next=nxt))['seg_logit'])
                 cur = nxt
-    model.train(was_training)
+    return outs
+
+
+def _vote_chunk_logits(outs, chunk_inds, n_pts, num_chunks, num_classes):
+    """infer_scene's tail: the batches' logits brought to one width, gathered over the ranks and voted into the scene."""
     # One common column count for the collective: the largest VALID length of any chunk of the scene -- known on every rank
     # from the (host-known) index lists, so no shape exchange is needed.  Columns beyond a chunk's own valid length are
     # never read by the vote, so cutting a longer (padded) chunk there loses nothing.
@@ -314,24 +331,143 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
     lengths, n_pts, dev = csr['lengths'], points.size(0), points.device
     if not lengths:
         return [], [], n_pts, []
+    batches, order, rows, picked, pixel_box = _bucketed_rows(csr, points, 'prepare_scene_bucketed', min_nb_pts, batch_size, max_batch_points, max_bucket,
+                                                             pad_seed)
+    batch = _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed', k, image_normalizer, channels_last)
+    chunk_batches, lo = [], 0
+    for (N, members), pts in zip(batches, rows):
+        hi = lo + len(members)
+        chunk_batches.append(batch(picked[lo:hi], pts, pixel_box[lo:hi]))
+        lo = hi
+    chunk_inds = torch.split(csr['index'], lengths)
+    return chunk_batches, [chunk_inds[c] for c in order], n_pts, order
+
+
+def _bucketed_rows(csr, points, who, min_nb_pts, batch_size, max_batch_points, max_bucket, pad_seed):
+    """What prepare_scene_bucketed and infer_scene_shared share behind _scene_chunks: plan_buckets and ONE ops.pack_chunks launch.
+    -> (batches, order: plan_buckets' result; rows: every batch's padded points (B,3,N), views of one buffer; picked (C,nv) and pixel_box
+    (C,4) in the batches' order)."""
+    lengths = csr['lengths']
     if min(lengths) < 1:
-        raise RuntimeError('prepare_scene_bucketed: a chunk without points (chunk_thresh must be at least 1)')
+        raise RuntimeError(who + ': a chunk without points (chunk_thresh must be at least 1)')
     batches, order = plan_buckets(lengths, min_nb_pts=min_nb_pts, batch_size=batch_size, max_batch_points=max_batch_points, max_bucket=max_bucket)
     out_base, out_len, at = [0] * len(lengths), [0] * len(lengths), 0
     for N, members in batches:
         for c in members:
             out_base[c], out_len[c], at = at, N, at + 3 * N
     packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len, seed=pad_seed)
-    batch = _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed', k, image_normalizer, channels_last)
-    order_t = torch.tensor(order, dtype=torch.int64).to(dev)
-    picked, pixel_box = csr['picked'][order_t], csr['pixel_box'][order_t]
-    chunk_batches, lo = [], 0
-    for N, members in batches:
-        hi, first = lo + len(members), out_base[members[0]]
-        chunk_batches.append(batch(picked[lo:hi], packed[first:first + len(members) * 3 * N].view(len(members), 3, N), pixel_box[lo:hi]))
+    order_t = torch.tensor(order, dtype=torch.int64).to(points.device)
+    rows = [packed[out_base[members[0]]:out_base[members[0]] + len(members) * 3 * N].view(len(members), 3, N) for N, members in batches]
+    return batches, order, rows, csr['picked'][order_t], csr['pixel_box'][order_t]
+
+
+def plan_store_groups(frames_of_batch, max_frames):
+    """Runs of consecutive batches that share one feature store (infer_scene_shared).  frames_of_batch: per batch, the frames its chunks
+    picked (any iterable of ints, repeats allowed); max_frames: the most distinct frames a store may hold.  Greedy: a run grows while the
+    union of its batches' frames stays within max_frames; a single batch that needs more is a run of its own.  Host arithmetic only; the
+    batches themselves never depend on the cap.  -> list of (first batch, one past the last, the run's distinct frames ascending)."""
+    max_frames = int(max_frames)
+    if max_frames < 1:
+        raise RuntimeError('plan_store_groups: max_frames must be at least 1 (a store that cannot hold one frame)')
+    runs, lo, hi, union = [], 0, 0, set()
+    for frames in frames_of_batch:
+        frames = {int(f) for f in frames}
+        if hi > lo and len(union | frames) > max_frames:
+            runs.append((lo, hi, sorted(union)))
+            lo, union = hi, set()
+        union |= frames
+        hi += 1
+    if hi > lo:
+        runs.append((lo, hi, sorted(union)))
+    return runs
+
+
+def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
+                       min_nb_pts=2048, overlap=None, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None, pad_seed=0, batch_size=32,
+                       max_batch_points=32 * 8192, max_bucket=32768, image_normalizer=None, channels_last=False, frame_batch=32,
+                       max_store_bytes=8 << 30):
+    """The whole-scene test of MVPNet (mvpnet/test_mvpnet_3d.py:142-174) from a scene's raw arrays with every frame through the 2D network
+    ONCE: `infer_scene(model, *prepare_scene_bucketed(...)[:3])` -- same chunks, same frames, same batches in the same order, same padded
+    points, same kernels behind the lift -- without its (B,nv,3,H,W) images per batch.  Single process.
+    model: an MVPNet3D; run in eval mode under no_grad, its mode is restored.  The other arguments are prepare_scene_bucketed's;
+    frame_batch: frames per forward of the 2D network; max_store_bytes: the most memory a feature store may take.
+
+    Neighbouring chunks pick largely the same frames, and in eval mode a frame's feature map does not depend on its batch neighbours (with
+    MIOpen its last bits may depend on the batch SIZE; an elementwise network's do not).  The batches are cut into runs of consecutive
+    batches whose distinct frames fit one store (plan_store_groups, max_store_bytes // (H*W*C*4) frames; host arithmetic on the picked
+    table -- the one device-to-host read beyond _scene_chunks' own --; the batch plan never depends on the cap).  Per run the distinct
+    frames go through model.net_2d once each (raw uint8 frames through ops.prepare_frames first, as in infer_scene_2d) into one
+    channels-last float32 store (U,H,W,C); the run's batches carry `feature_store` / `view_slot` in place of `images`, so MVPNet3D lifts
+    with ops.lift_store -- no 2D forward, no channels-last copy per batch --, the next batch's geometry prefetched as infer_scene does; the
+    store is released before the next run's is made.  A frame two runs share runs once per run.
+    -> mean logits (n_pts,C), labels (n_pts,) with C where no chunk holds the point, counts (n_pts,) int32, as infer_scene.  A scene with
+    no kept window gives zeros, labels all C, counts zero, and nothing goes through the 2D network."""
+    dev, n_pts, nv = points.device, points.size(0), int(num_rgbd_frames)
+    if frame_batch < 1:
+        raise RuntimeError('infer_scene_shared: frame_batch must be at least 1')
+    net = model.module if hasattr(model, 'module') else model
+    net_2d, num_classes, C = net.net_2d, int(net.net_3d.num_classes), int(net.feat_aggreg.in_channels)
+    csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
+                        num_base_pts, radius, generator)
+    lengths = csr['lengths']
+    if not lengths:
+        return (torch.zeros((n_pts, num_classes), dtype=torch.float32, device=dev), torch.full((n_pts,), num_classes, dtype=torch.int64, device=dev),
+                torch.zeros((n_pts,), dtype=torch.int32, device=dev))
+    ldepth, cam, kinv = _scene_cameras(dev, depth, cam_matrix, images, lift_depth, 'infer_scene_shared', image_normalizer, channels_last)
+    F, H, W = ldepth.shape
+    batches, order, rows, picked, pixel_box = _bucketed_rows(csr, points, 'infer_scene_shared', min_nb_pts, batch_size, max_batch_points, max_bucket,
+                                                             pad_seed)
+    picked_host = picked.cpu().tolist()  # (the one read)
+    chunk_batches, sels, frames_of_batch, lo = [], [], [], 0
+    for (_, members), pts in zip(batches, rows):  # prepare_scene_bucketed's batches without `images`
+        hi = lo + len(members)
+        sel = picked[lo:hi]
+        chunk_batches.append({'depth': ldepth[sel].contiguous(), 'pose': pose[sel].contiguous(), 'points': pts, 'cam_matrix': cam[sel].contiguous(),
+                              'kinv': kinv[sel].contiguous(), 'pixel_box': pixel_box[lo:hi].contiguous(), 'k': int(k)})
+        sels.append(sel)
+        frames_of_batch.append({f for row in picked_host[lo:hi] for f in row})
         lo = hi
+    runs = plan_store_groups(frames_of_batch, int(max_store_bytes) // (H * W * C * 4))
+    run_of_batch = {first: r for r, (first, _, _) in enumerate(runs)}
+    state = {'store': None, 'slot_of': None}
+
+    def run_2d(frames):  # (b,) int64 on the device -> (b,C,H,W)
+        if images.dtype == torch.uint8:
+            x = ops.prepare_frames(images, frames, normalizer=image_normalizer, channels_last=channels_last)
+        else:
+            x = images[frames].contiguous()
+        out = net_2d({'image': x})['feature']
+        if not torch.is_tensor(out) or out.dim() != 4 or tuple(out.shape) != (frames.numel(), C, H, W) or out.dtype != torch.float32:
+            raise RuntimeError('infer_scene_shared: net_2d must return float32 feature (b,{},{},{}): the aggregation\'s channels at the lifting '
+                               'maps\' size'.format(C, H, W))
+        return out
+
+    def ready(i, batch):
+        """Batch i as the model takes it; the first batch of a run makes the run's store (the previous one is released first)."""
+        if i in run_of_batch:
+            distinct = runs[run_of_batch[i]][2]
+            state['store'] = state['slot_of'] = None
+            frames = torch.tensor(distinct, dtype=torch.int64).to(dev)
+            # channels-last memory whatever the network writes: the copy into the store makes a neighbour's C features one contiguous row
+            store = torch.empty((len(distinct), H, W, C), dtype=torch.float32, device=dev)
+            for lo in range(0, len(distinct), int(frame_batch)):
+                out = run_2d(frames[lo:lo + int(frame_batch)])
+                store[lo:lo + out.size(0)].permute(0, 3, 1, 2).copy_(out)
+            slot_of = torch.full((F,), -1, dtype=torch.int32, device=dev)
+            slot_of[frames] = torch.arange(len(distinct), dtype=torch.int32, device=dev)
+            state['store'], state['slot_of'] = store, slot_of
+        return dict(batch, feature_store=state['store'], view_slot=state['slot_of'][sels[i]].contiguous())
+
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            outs = _forward_batches(model, chunk_batches, ready)
+    finally:
+        state.clear()
+        model.train(was_training)
     chunk_inds = torch.split(csr['index'], lengths)
-    return chunk_batches, [chunk_inds[c] for c in order], n_pts, order
+    return _vote_chunk_logits(outs, [chunk_inds[c] for c in order], n_pts, len(order), num_classes)
 
 
 def infer_scene_2d(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
