@@ -460,6 +460,25 @@ int mvp_pack_chunks_f32(const float* points, int64_t n, const int64_t* index, in
                         const int64_t* out_base, const int64_t* out_len, const int64_t* host_lengths, const int64_t* host_out_len,
                         uint64_t seed, float* out, int64_t out_floats, mvp_stream_t stream);
 
+/* mvp_pack_chunks_f32 with a per-point feature beside the coordinates and the chunks placed in SLOTS: the batches of the 3D baselines'
+ * sliding-window test (mvpnet/test_3d_chunks.py:106-167), one launch for a whole scene.  Chunk c's N_c = out_len[c] slots start at slot
+ * slot_base[c] ((C,) int64 on the device): its points are the (3,N_c) matrix at out_points + 3*slot_base[c], its features the (Cf,N_c)
+ * matrix at out_feature + Cf*slot_base[c] -- chunks of one N_c in consecutive slots are a (B,3,N_c) and a (B,Cf,N_c) batch, as PN2SSG
+ * reads them.  The member of a slot is mvp_pack_chunks_f32's, computed ONCE per slot: a duplicate carries its source point's feature,
+ * and out_points is bit-identical to what mvp_pack_chunks_f32 writes with out_base = 3*slot_base.  The feature source is one of
+ *   colors (n,3) uint8: out = (float)c / 255.0f, an IEEE division (mvp_gather_cloud_f32's expression, scannet_3d.py:82), Cf must be 3;
+ *   feature (n,Cf) float32, 1 <= Cf <= MVP_PACK_CLOUD_MAX_CHANNELS: copied bit for bit;
+ *   neither (both NULL): only the points are written, Cf is not looked at and out_feature may be NULL.
+ * out_slots: the slots the buffers hold (3*out_slots and Cf*out_slots floats); a chunk whose slots would leave them, or whose slice of
+ * index is empty, is not written at all; point indices are clamped into [0, n).  host_lengths, host_out_len, seed: as
+ * mvp_pack_chunks_f32.  MVP_EINVAL unless n, total >= 1, C, out_slots >= 0, N_c >= n_c >= 1, at most one feature source and a Cf that
+ * fits it; MVP_EUNSUPPORTED for n >= 2^31, C > MVP_CHUNKER_MAX_WINDOWS, N_c >= 2^31 or Cf > MVP_PACK_CLOUD_MAX_CHANNELS. */
+#define MVP_PACK_CLOUD_MAX_CHANNELS 8
+int mvp_pack_cloud_f32(const float* points, const uint8_t* colors, const float* feature, int64_t Cf, int64_t n, const int64_t* index,
+                       int64_t total, const int64_t* offsets, int64_t C, const int64_t* slot_base, const int64_t* out_len,
+                       const int64_t* host_lengths, const int64_t* host_out_len, uint64_t seed, float* out_points, float* out_feature,
+                       int64_t out_slots, mvp_stream_t stream);
+
 /* ---- frames (NEW on the device; the reference prepares every frame in a data-loader worker) ----
  * The picked frames of a raw uint8 store as the 2D network reads them: T.ColorJitter(brightness, contrast, saturation) on the PIL
  * image, `/ 255.`, `(image - mean) / std`, np.fliplr (mvpnet/data/scannet_2d3d.py:241-252, :293-296; mvpnet/data/scannet_2d.py:158-171).
@@ -1196,6 +1215,43 @@ int mvp_seg_loss_backward_f32(const float* logit, int64_t B, int64_t C, int64_t 
                               mvp_stream_t stream);
 int mvp_seg_confusion_f32(const float* logit, int64_t B, int64_t C, int64_t N, int64_t ld_b, int64_t ld_c, int64_t ld_n,
                           const int64_t* label, int64_t ignore_index, int64_t* mat, mvp_stream_t stream);
+
+/* ---- scene results: the model ensemble and the evaluator's confusion matrix (NEW on the device) ----
+ * mvp_ensemble_softmax_f32: mvpnet/ensemble.py:45-49 -- `sum_m scipy.special.softmax(logit_m, axis=1)`, then argmax -- in ONE launch.
+ *   logits: a HOST array of M device pointers, 1 <= M <= MVP_ENSEMBLE_MAX_MODELS (handed to the kernel by value: no pointer table on the
+ *   device, no stacked copy); model m's element (r,c) is at logits[m][r*ld_r + c*ld_c], the strides common to all models: (n,C) rows,
+ *   the transposed view of a (C,n) network output and rows with a padded stride go in as they lie.  1 <= C <= 64, n < 2^31.
+ *   prob (n,C) float32, contiguous, or NULL; label (n,) int64.
+ * Definition (pinned).  All arithmetic in float32, every operation rounded once, never contracted; per row:
+ *     per model m:   mx = max_c x_c                         (NaN-propagating, as numpy.max)
+ *                    e_c = expf(x_c - mx)                   (the accurate library expf, no fast intrinsic)
+ *                    s = ((e_0 + e_1) + ...) + e_{C-1}      in class order
+ *                    p_c = e_c / s                          an IEEE division
+ *     over models:   P_c = ((p0_c + p1_c) + ...)            in model order;   prob[r,c] = P_c
+ *     label[r] = the first maximum of P: by strict `>` from P_0.
+ *   A NaN anywhere in a model's row makes mx, hence every e_c, s and p_c of that model NaN: the whole P row is NaN and the label is 0
+ *   (numpy.argmax's answer for an all-NaN row).  An infinite logit gives what the expression gives (+inf: inf - inf = NaN, the row as
+ *   above; a row of -inf likewise).  No fault and no hang for any input; no atomics, the same bits every run.
+ *   Rows are read with 16-byte loads when ld_c == 1, C % 4 == 0, ld_r % 4 == 0 and every pointer (prob included) is 16-byte aligned,
+ *   one dword per element otherwise.
+ * Before any launch: MVP_ENULL (logits, one of its first M entries, label), MVP_EINVAL unless M, C >= 1 and n, ld_r, ld_c >= 0,
+ * MVP_EUNSUPPORTED for M > MVP_ENSEMBLE_MAX_MODELS, C > 64 or n >= 2^31.  n == 0: nothing is launched.
+ *
+ * mvp_label_confusion_i64: evaluate_3d.py:25-40 -- sklearn's confusion_matrix(gt, pred, labels=...) added to a running matrix.
+ *   pred, gt (n,) int64; pred_lut (Lp,), gt_lut (Lg,) int32 or NULL (with L = 0): value -> position among the evaluator's labels.
+ *     position of v: with a table, lut[v] for 0 <= v < L, else -1 (a table entry outside [0,C) is -1 as well);
+ *                    without one, v for 0 <= v < C, else -1.
+ *   mat (C,C) int64 += 1 at [position(gt)][position(pred)] where both are >= 0: ignored ground truth (-100), raw ids that are no
+ *   evaluation class and the "no prediction" label drop out.  Integer sums (a per-workgroup histogram for C <= 64, global atomics
+ *   beyond): the same bits every run.
+ * Before any launch: MVP_ENULL (pred, gt, mat), MVP_EINVAL unless n >= 0, C >= 1 and each table comes with its length (NULL <=> 0),
+ * MVP_EUNSUPPORTED for C > MVP_CONFUSION_MAX_CLASSES.  n == 0: nothing is launched. */
+#define MVP_ENSEMBLE_MAX_MODELS 8
+#define MVP_CONFUSION_MAX_CLASSES 32768
+int mvp_ensemble_softmax_f32(const float* const* logits, int64_t M, int64_t n, int64_t C, int64_t ld_r, int64_t ld_c, float* prob,
+                             int64_t* label, mvp_stream_t stream);
+int mvp_label_confusion_i64(const int64_t* pred, const int64_t* gt, int64_t n, int64_t C, const int32_t* pred_lut, int64_t Lp,
+                            const int32_t* gt_lut, int64_t Lg, int64_t* mat, mvp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,9 @@ _SIGNATURES = {
     'mvp_scene_chunks_count_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _ptr],
     'mvp_scene_chunks_fill_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr],
     'mvp_pack_chunks_f32': [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _ptr, _i64, _ptr],
+    'mvp_pack_cloud_f32': [_ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _ptr, _ptr, _i64, _ptr],
+    'mvp_ensemble_softmax_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
+    'mvp_label_confusion_i64': [_ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr],
     'mvp_prepare_frames_u8': [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr],
     'mvp_resize_bilinear_table': [_i64, _i64, _ptr, _ptr, _ptr, _ptr],  # (host only: no stream)
     'mvp_resize_nearest_table': [_i64, _i64, _ptr],  # (host only: no stream)

@@ -1,7 +1,7 @@
 // chunker.hip -- the sliding-window chunker of a whole scene and the packing of its (ragged) chunks into padded batches, for gfx950:
 // scene2chunks_legacy (mvpnet/utils/chunk_util.py:4-53) without the (windows x points) membership matrices, and the sparse-chunk rule of
 // mvpnet/test_mvpnet_3d.py:146-154 for all chunks of a scene in one launch.  Definitions: include/mvp_hip.h (mvp_scene_chunks_*,
-// mvp_pack_chunks_f32).
+// mvp_pack_chunks_f32, mvp_pack_cloud_f32).
 //
 //   chunks_count_kernel : one workgroup per window walks all points once; per thread two integer counters (inner / outer test), one
 //                         reduction at the end -- integers, no atomics.
@@ -11,6 +11,8 @@
 //                         (the pattern of sample.hip's select_kernel<0> and of ball_query.hip).  The z extent rides along; the
 //                         base-point bits are chunk_common.h's write_base_bits.
 //   chunks_pack_kernel  : slot s of chunk c -> a member (chunk_common.h's pad rule) -> three coordinates.
+//   chunks_pack_cloud_kernel : the same slot -> member rule, computed once per slot, -> three coordinates and the point's feature row
+//                         (colours / 255 or float channels): the 3D baselines' (B,3,N) + (B,Cf,N) batches.
 // Every window re-reads the scene (12 bytes x n, out of L2 after the first): a per-point scatter into its windows would read less but
 // needs a stable multi-split.
 #include "chunk_common.h"
@@ -213,6 +215,48 @@ __global__ __launch_bounds__(kChkThreads) void chunks_pack_kernel(const float* _
   }
 }
 
+// chunks_pack_kernel with the chunks placed in SLOTS and a per-point feature beside the coordinates: the member of a slot is computed once
+// and both rows are read through it.  kColors: (n,3) uint8 written as c / 255 (mvp_gather_cloud_f32's expression); else (n,Cf) float32 rows
+// copied as they are; Cf = 0: coordinates only.
+struct PackCloudArgs {
+  const float* points;
+  const uint8_t* colors;
+  const float* feature;
+  const int64_t* index;
+  const int64_t* offsets;
+  const int64_t* slot_base;
+  const int64_t* out_len;
+  float* out_points;
+  float* out_feature;
+  int64_t n, total, out_slots;
+  uint32_t seed32;
+  int Cf;
+};
+
+template <bool kColors>
+__global__ __launch_bounds__(kChkThreads) void chunks_pack_cloud_kernel(PackCloudArgs a) {
+  const int c = blockIdx.y;
+  int64_t off = a.offsets[c], end = a.offsets[c + 1];
+  clamp_slice(off, end, a.total);
+  const int64_t nc = end - off, N = a.out_len[c], sb = a.slot_base[c];
+  // the chunk's N slots lie inside the buffers, or nothing of it is written
+  if (N <= 0 || nc <= 0 || nc >= (1ll << 32) || sb < 0 || sb > a.out_slots || N > a.out_slots - sb) return;
+  const uint32_t sc = chunk_seed(a.seed32, c);
+  float* __restrict__ op = a.out_points + 3 * sb;
+  float* __restrict__ of = a.out_feature + (int64_t)a.Cf * sb;
+  for (int64_t s = (int64_t)blockIdx.x * kChkThreads + threadIdx.x; s < N; s += (int64_t)gridDim.x * kChkThreads) {
+    const int64_t p = clamp_index(a.index[off + pad_member(s, nc, sc)], a.n);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) op[k * N + s] = a.points[p * 3 + k];
+    if (kColors) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) of[k * N + s] = (float)a.colors[p * 3 + k] / 255.0f;  // IEEE division
+    } else {
+      for (int k = 0; k < a.Cf; ++k) of[k * N + s] = a.feature[p * a.Cf + k];
+    }
+  }
+}
+
 inline bool chunker_shape_ok(int64_t n, int64_t nc, int64_t nb) {
   return n < (1ll << 31) && nc <= MVP_CHUNKER_MAX_WINDOWS && nb <= MVP_OVERLAP_MAX_BASE;
 }
@@ -282,5 +326,42 @@ MVP_API int mvp_pack_chunks_f32(const float* points, int64_t n, const int64_t* i
   const uint32_t seed32 = (uint32_t)(seed ^ (seed >> 32));
   hipLaunchKernelGGL(chunks_pack_kernel, dim3((unsigned)(gx > 1024 ? 1024 : gx), (unsigned)C), dim3(kChkThreads), 0, static_cast<hipStream_t>(stream),
                      points, n, index, total, offsets, out_base, out_len, seed32, out_floats, out);
+  return mvp_launch_status();
+}
+
+MVP_API int mvp_pack_cloud_f32(const float* points, const uint8_t* colors, const float* feature, int64_t Cf, int64_t n, const int64_t* index,
+                               int64_t total, const int64_t* offsets, int64_t C, const int64_t* slot_base, const int64_t* out_len,
+                               const int64_t* host_lengths, const int64_t* host_out_len, uint64_t seed, float* out_points, float* out_feature,
+                               int64_t out_slots, mvp_stream_t stream) {
+  MVP_NONNULL(points);
+  MVP_NONNULL(index);
+  MVP_NONNULL(offsets);
+  MVP_NONNULL(slot_base);
+  MVP_NONNULL(out_len);
+  MVP_NONNULL(host_lengths);
+  MVP_NONNULL(host_out_len);
+  MVP_NONNULL(out_points);
+  const bool has_feature = colors != nullptr || feature != nullptr;
+  if (has_feature) MVP_NONNULL(out_feature);
+  MVP_REQUIRE(n >= 1 && total >= 1 && C >= 0 && out_slots >= 0 && !(colors != nullptr && feature != nullptr));
+  MVP_REQUIRE(!has_feature || (colors != nullptr ? Cf == 3 : Cf >= 1));
+  int64_t widest = 0;
+  for (int64_t c = 0; c < C; ++c) {
+    MVP_REQUIRE(host_lengths[c] >= 1 && host_out_len[c] >= host_lengths[c]);
+    widest = host_out_len[c] > widest ? host_out_len[c] : widest;
+  }
+  if (n >= (1ll << 31) || C > MVP_CHUNKER_MAX_WINDOWS || widest >= (1ll << 31) || (has_feature && Cf > MVP_PACK_CLOUD_MAX_CHANNELS))
+    return MVP_EUNSUPPORTED;
+  if (C == 0) return MVP_OK;
+  PackCloudArgs a;
+  a.points = points, a.colors = colors, a.feature = feature, a.index = index, a.offsets = offsets, a.slot_base = slot_base, a.out_len = out_len;
+  a.out_points = out_points, a.out_feature = out_feature, a.n = n, a.total = total, a.out_slots = out_slots;
+  a.seed32 = (uint32_t)(seed ^ (seed >> 32)), a.Cf = has_feature ? (int)Cf : 0;
+  const int64_t gx = cdiv(widest, kChkThreads);
+  const dim3 grid((unsigned)(gx > 1024 ? 1024 : gx), (unsigned)C), block(kChkThreads);
+  if (colors != nullptr)
+    hipLaunchKernelGGL(chunks_pack_cloud_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL(chunks_pack_cloud_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), a);
   return mvp_launch_status();
 }

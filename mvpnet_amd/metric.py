@@ -2,6 +2,7 @@
 
   SegAccuracy, SegIoU           mvpnet/models/metric.py:5-73   (same names, `update_dict` contract, strings)
   Evaluator, CLASS_NAMES, ...   mvpnet/evaluate_3d.py:4-92     (confusion matrix + accuracy / IoU numbers only)
+  DeviceEvaluator               the same for label tensors on the device (mvp_label_confusion_i64; nothing is read back until a number is)
 
 MI355X side: for fp32 logits on the GPU both meters get `argmax -> mask by ignore_index -> bincount` from ONE pass of
 `mvp_seg_confusion_f32` over the logits where the network left them ((B,C,N) or channels-last rows); the reference runs
@@ -182,3 +183,58 @@ class Evaluator(object):
     @property
     def overall_iou(self):
         return np.nanmean(self.class_iou)
+
+
+class DeviceEvaluator(object):
+    """Evaluator for label tensors that are on the device already (the four whole-scene test paths of mvpnet_amd.scene and
+    scene.ensemble_scene end there): the same interface and numbers, with the confusion matrix kept on the device.  `update` only
+    launches (ops.label_confusion: mvp_label_confusion_i64 through two value -> position tables built once here); nothing is copied or
+    synchronised until a number -- or `confusion_matrix` -- is read, and that read is the only synchronisation.
+    `labels` must be non-negative integers (raw ids index the tables), one per class.  For such labels the reference's early return on
+    a scene whose ground truth is all negative (evaluate_3d.py:29-31) adds nothing to the matrix -- a negative value is no label -- and
+    neither does the kernel: there is no such test here, and no 'Invalid label.' print.  Ignored ground truth (-100), raw ids that are
+    no evaluation class and the "no prediction" label (num_classes, when it is not itself one of `labels`) drop out, as in Evaluator.
+    Host arrays are refused: Evaluator exists for them."""
+
+    def __init__(self, class_names, labels=None):
+        self.class_names = tuple(class_names)
+        self.num_classes = n = len(self.class_names)
+        labels = np.arange(n) if labels is None else np.asarray(labels)
+        if labels.shape != (n,):
+            raise ValueError('one label id per class expected')
+        if not np.issubdtype(labels.dtype, np.integer) or (labels < 0).any():
+            raise ValueError('DeviceEvaluator: labels must be non-negative integers')
+        self.labels = labels
+        lut = np.full(int(labels.max()) + 1 if n else 1, -1, np.int32)
+        for pos in range(n - 1, -1, -1):  # (a repeated id keeps its first position, as Evaluator's stable sort does)
+            lut[labels[pos]] = pos
+        self._host_lut = torch.from_numpy(lut)
+        self._lut = self._mat = None
+
+    def update(self, pred_label, gt_label):
+        from . import ops
+        for t in (pred_label, gt_label):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError('DeviceEvaluator.update takes tensors on the GPU; use metric.Evaluator for host arrays')
+        if self._mat is None:
+            self._lut = self._host_lut.to(pred_label.device)
+            self._mat = torch.zeros((self.num_classes, self.num_classes), dtype=torch.int64, device=pred_label.device)
+        pred, gt = pred_label.reshape(-1).long().contiguous(), gt_label.reshape(-1).long().contiguous()
+        ops.label_confusion(pred, gt, self._mat, pred_lut=self._lut, gt_lut=self._lut)
+
+    def batch_update(self, pred_labels, gt_labels):
+        if len(pred_labels) != len(gt_labels):
+            raise ValueError('one prediction array per ground-truth array expected')
+        for p, g in zip(pred_labels, gt_labels):
+            self.update(p, g)
+
+    @property
+    def confusion_matrix(self):
+        """(C,C) float64 NumPy array, as Evaluator's (the read: one device-to-host copy)."""
+        n = self.num_classes
+        return np.zeros((n, n)) if self._mat is None else self._mat.cpu().numpy().astype(np.float64)
+
+    overall_acc = Evaluator.overall_acc
+    class_seg_acc = Evaluator.class_seg_acc
+    class_iou = Evaluator.class_iou
+    overall_iou = Evaluator.overall_iou

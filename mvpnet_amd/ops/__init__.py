@@ -11,13 +11,15 @@ from .overlap import rgbd_overlap, select_frames_batched, pack_bits, unpack_bits
 from .vote import vote_nearest, lift_vote
 from .sample import sample_chunks
 from .scene_sample import sample_scenes, gather_cloud
-from .chunker import scene_chunks, pack_chunks
+from .chunker import scene_chunks, pack_chunks, pack_cloud
+from .ensemble import ensemble_softmax, label_confusion
 from .frames import prepare_frames
 from .resize import resize_frames, prepare_labels
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
            'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'lift_store', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
            'pack_bits', 'unpack_bits', 'vote_nearest', 'lift_vote', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
+           'pack_cloud', 'ensemble_softmax', 'label_confusion',
            'prepare_frames', 'resize_frames', 'prepare_labels']
 
 

@@ -7,6 +7,7 @@ from .. import _lib as L
 from .overlap import MAX_BASE_POINTS  # MVP_OVERLAP_MAX_BASE
 
 MAX_WINDOWS = 65535  # MVP_CHUNKER_MAX_WINDOWS
+MAX_CLOUD_CHANNELS = 8  # MVP_PACK_CLOUD_MAX_CHANNELS
 
 
 def supported(n, nc, nb=0):
@@ -98,3 +99,50 @@ def pack_chunks(points, index, offsets, lengths, out_base, out_len, seed=0):
     L.call('mvp_pack_chunks_f32', points, L.ptr(points), points.size(0), L.ptr(index), index.numel(), L.ptr(offsets), C, L.ptr(dev_table[0]),
            L.ptr(dev_table[1]), host[0].ctypes.data, host[2].ctypes.data, int(seed) & (2 ** 64 - 1), L.ptr(out), out_floats)
     return out
+
+
+def pack_cloud(points, index, offsets, lengths, slot_base, out_len, colors=None, feature=None, seed=0):
+    """pack_chunks with a per-point feature beside the coordinates, one launch: what the 3D baselines' sliding-window test feeds PN2SSG.
+    points, index, offsets, lengths, out_len, seed: as pack_chunks.  slot_base: C host ints, the chunks' places in SLOTS -- chunk c's
+    points are the (3, out_len[c]) matrix at float 3 * slot_base[c] of `points_flat`, its features the (Cf, out_len[c]) matrix at float
+    Cf * slot_base[c] of `feature_flat`; chunks of one length in consecutive slots are a (B,3,N) and a (B,Cf,N) batch.
+    colors (n,3) uint8 -> colors / 255 (Cf = 3), or feature (n,Cf) float32, 1 <= Cf <= 8, copied; at most one of them.  A padded slot
+    repeats one member's point AND feature.  -> (points_flat, feature_flat or None); points_flat holds the bits pack_chunks writes
+    with out_base = 3 * slot_base.  Definition (pinned): include/mvp_hip.h, mvp_pack_cloud_f32."""
+    L.require_gpu(points, index, offsets, colors, feature)
+    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32 or points.size(0) < 1:
+        raise RuntimeError('pack_cloud: points must be (n,3) float32, n >= 1')
+    if index.dtype != torch.int64 or index.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError('pack_cloud: index must be (total,) int64 and offsets (C+1,) int64')
+    if index.device != points.device or offsets.device != points.device:
+        raise RuntimeError('pack_cloud: points, index and offsets must be on one device')
+    if colors is not None and feature is not None:
+        raise RuntimeError('pack_cloud: colors or feature, not both')
+    n, Cf = points.size(0), 0
+    if colors is not None:
+        if colors.dtype != torch.uint8 or tuple(colors.shape) != (n, 3) or colors.device != points.device:
+            raise RuntimeError('pack_cloud: colors must be (n,3) uint8 on the points\' device')
+        Cf = 3
+    if feature is not None:
+        if feature.dtype != torch.float32 or feature.dim() != 2 or feature.size(0) != n or not 1 <= feature.size(1) <= MAX_CLOUD_CHANNELS \
+                or feature.device != points.device:
+            raise RuntimeError('pack_cloud: feature must be (n,Cf) float32 on the points\' device, 1 <= Cf <= {}'.format(MAX_CLOUD_CHANNELS))
+        Cf = feature.size(1)
+    C = offsets.numel() - 1
+    if not (len(lengths) == len(slot_base) == len(out_len) == C):
+        raise RuntimeError('pack_cloud: lengths, slot_base and out_len must have one entry per chunk ({})'.format(C))
+    host = np.array([lengths, slot_base, out_len], dtype=np.int64).reshape(3, -1)
+    if C and (host[0].min() < 1 or (host[2] < host[0]).any() or host[1].min() < 0):
+        raise RuntimeError('pack_cloud: needs out_len[c] >= lengths[c] >= 1 and slot_base[c] >= 0')
+    out_slots = int((host[1] + host[2]).max()) if C else 0
+    out_points = torch.empty(3 * out_slots, dtype=torch.float32, device=points.device)
+    out_feature = torch.empty(Cf * out_slots, dtype=torch.float32, device=points.device) if Cf else None
+    if C == 0:
+        return out_points, out_feature
+    if int(host[0].sum()) > index.numel():
+        raise RuntimeError('pack_cloud: the chunks list {} points but index has {}'.format(int(host[0].sum()), index.numel()))
+    dev_table = torch.from_numpy(host[1:]).to(points.device)  # (2,C): slot_base, out_len
+    L.call('mvp_pack_cloud_f32', points, L.ptr(points), L.ptr(colors), L.ptr(feature), Cf, n, L.ptr(index), index.numel(), L.ptr(offsets), C,
+           L.ptr(dev_table[0]), L.ptr(dev_table[1]), host[0].ctypes.data, host[2].ctypes.data, int(seed) & (2 ** 64 - 1), L.ptr(out_points),
+           L.ptr(out_feature), out_slots)
+    return out_points, out_feature

@@ -348,17 +348,90 @@ def _bucketed_rows(csr, points, who, min_nb_pts, batch_size, max_batch_points, m
     -> (batches, order: plan_buckets' result; rows: every batch's padded points (B,3,N), views of one buffer; picked (C,nv) and pixel_box
     (C,4) in the batches' order)."""
     lengths = csr['lengths']
+    batches, order, slot_base, out_len = _bucket_slots(lengths, who, min_nb_pts, batch_size, max_batch_points, max_bucket)
+    packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, [3 * s for s in slot_base], out_len, seed=pad_seed)
+    order_t = torch.tensor(order, dtype=torch.int64).to(points.device)
+    return batches, order, _batch_views(packed, 3, batches, slot_base), csr['picked'][order_t], csr['pixel_box'][order_t]
+
+
+def _bucket_slots(lengths, who, min_nb_pts, batch_size, max_batch_points, max_bucket):
+    """The bucket and placement planning of every bucketed path (_bucketed_rows, infer_scene_3d): plan_buckets, and the batches laid one
+    after the other in SLOTS (one slot = one padded point).  -> (batches, order: plan_buckets' result; slot_base, out_len: per chunk, in
+    the chunker's numbering, its first slot and its padded size).  Host arithmetic only."""
     if min(lengths) < 1:
         raise RuntimeError(who + ': a chunk without points (chunk_thresh must be at least 1)')
     batches, order = plan_buckets(lengths, min_nb_pts=min_nb_pts, batch_size=batch_size, max_batch_points=max_batch_points, max_bucket=max_bucket)
-    out_base, out_len, at = [0] * len(lengths), [0] * len(lengths), 0
+    slot_base, out_len, at = [0] * len(lengths), [0] * len(lengths), 0
     for N, members in batches:
         for c in members:
-            out_base[c], out_len[c], at = at, N, at + 3 * N
-    packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len, seed=pad_seed)
-    order_t = torch.tensor(order, dtype=torch.int64).to(points.device)
-    rows = [packed[out_base[members[0]]:out_base[members[0]] + len(members) * 3 * N].view(len(members), 3, N) for N, members in batches]
-    return batches, order, rows, csr['picked'][order_t], csr['pixel_box'][order_t]
+            slot_base[c], out_len[c], at = at, N, at + N
+    return batches, order, slot_base, out_len
+
+
+def _batch_views(flat, channels, batches, slot_base):
+    """Every batch's (B,channels,N) view of a flat buffer packed by _bucket_slots' placement."""
+    return [flat[channels * slot_base[members[0]]:channels * (slot_base[members[0]] + len(members) * N)].view(len(members), channels, N)
+            for N, members in batches]
+
+
+def infer_scene_3d(model, points, colors=None, *, chunk_size=(1.5, 1.5), chunk_stride=0.5, chunk_thresh=1000, chunk_margin=(0.2, 0.2), min_nb_pts=2048,
+                   use_color=None, batch_size=32, max_batch_points=32 * 8192, max_bucket=32768, pad_seed=0):
+    """The sliding-window test of the 3D baselines (mvpnet/test_3d_chunks.py:106-167; configs/scannet/3d_baselines/pn2ssg_chunk.yaml,
+    pn2ssg_rgb_chunk.yaml) from a scene's points [and colours]; the defaults are the script's.  Single process.
+    model: a PN2SSG, or anything that maps {'points' (B,3,N) [, 'feature' (B,3,N)]} to {'seg_logit' (B,C,N)} and has `num_classes`; run in
+    eval mode under no_grad, its mode is restored.  points (n,3) float32 on the device.  colors (n,3): uint8 as the stores hold them
+    (the pack kernel writes colors / 255, scannet_3d.py:82) or float32 already divided by 255.  use_color: None = `model.in_channels == 3`
+    (:95); a model that wants colours without `colors` raises before any launch.
+
+    The reference feeds the chunks one at a time, every chunk with all its points, padded to min_nb_pts by transforms.Pad
+    (transforms.py:136-148: uniform duplicates of the chunk's own points behind the originals).  Here chunks of similar size share a
+    batch after padding to a common size by the same law (plan_buckets through _bucket_slots, as prepare_scene_bucketed; a duplicate
+    carries its source point's colour) -- exact in eval mode, see prepare_scene_bucketed.  Steps: chunks.scene2chunks_csr without base
+    points (its two host reads -- the scene's extent and the windows' counts -- are the only ones), ONE ops.pack_cloud launch writes every
+    batch's points and features, _forward_batches, _vote_chunk_logits (the atomics-free vote, adding in the batches' order).
+    -> mean logits (n,C), labels (n,) with C where no chunk holds the point, counts (n,) int32.  A scene with no kept window gives zeros,
+    labels all C and counts zero, and nothing goes through the model."""
+    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32 or not points.is_cuda:
+        raise RuntimeError('infer_scene_3d: points must be (n,3) float32 on the device')
+    net = model.module if hasattr(model, 'module') else model
+    dev, n_pts, num_classes = points.device, points.size(0), int(net.num_classes)
+    use_color = (getattr(net, 'in_channels', 0) == 3) if use_color is None else bool(use_color)
+    source = {}
+    if use_color:
+        if colors is None:
+            raise RuntimeError('infer_scene_3d: the model reads colours (in_channels = 3 / use_color) but no colors were given')
+        if colors.dim() != 2 or tuple(colors.shape) != (n_pts, 3) or colors.dtype not in (torch.uint8, torch.float32) or colors.device != dev:
+            raise RuntimeError('infer_scene_3d: colors must be (n,3) uint8, or float32 already divided by 255, on the points\' device')
+        source = {'colors' if colors.dtype == torch.uint8 else 'feature': colors.contiguous()}
+    csr = CH.scene2chunks_csr(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin)
+    lengths = csr['lengths']
+    if not lengths:
+        return (torch.zeros((n_pts, num_classes), dtype=torch.float32, device=dev), torch.full((n_pts,), num_classes, dtype=torch.int64, device=dev),
+                torch.zeros((n_pts,), dtype=torch.int32, device=dev))
+    batches, order, slot_base, out_len = _bucket_slots(lengths, 'infer_scene_3d', min_nb_pts, batch_size, max_batch_points, max_bucket)
+    flat_points, flat_feature = ops.pack_cloud(points.contiguous(), csr['index'], csr['offsets'], lengths, slot_base, out_len, seed=pad_seed, **source)
+    chunk_batches = [{'points': p} for p in _batch_views(flat_points, 3, batches, slot_base)]
+    if use_color:
+        for b, f in zip(chunk_batches, _batch_views(flat_feature, 3, batches, slot_base)):
+            b['feature'] = f
+    was_training = model.training
+    model.eval()
+    try:
+        outs = _forward_batches(model, chunk_batches)
+    finally:
+        model.train(was_training)
+    chunk_inds = torch.split(csr['index'], lengths)
+    return _vote_chunk_logits(outs, [chunk_inds[c] for c in order], n_pts, len(order), num_classes)
+
+
+def ensemble_scene(logits_per_model, want_prob=True):
+    """The model ensemble of mvpnet/ensemble.py:45-49 on a scene: logits_per_model: the `mean` logits (n,C) that 1..8 models' runs of any
+    whole-scene test path (infer_scene, infer_scene_shared, infer_scene_2d, infer_scene_votes, infer_scene_3d) returned for ONE scene.
+    -> (prob (n,C): the sum of the models' softmaxes, or None; label (n,) int64: its argmax, first maximum).  One launch
+    (ops.ensemble_softmax), no stacked copy.  Unlike a test path's labels these have no "no prediction" class: a point no chunk holds has
+    zero logits in every model, hence equal probabilities and label 0, exactly as the reference's script treats its saved logits.  Raw
+    ids for a submission: `scannet_to_nyu40[label]`, plain tensor indexing."""
+    return ops.ensemble_softmax(logits_per_model, want_prob=want_prob)
 
 
 def plan_store_groups(frames_of_batch, max_frames):
