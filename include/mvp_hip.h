@@ -1253,6 +1253,51 @@ int mvp_ensemble_softmax_f32(const float* const* logits, int64_t M, int64_t n, i
 int mvp_label_confusion_i64(const int64_t* pred, const int64_t* gt, int64_t n, int64_t C, const int32_t* pred_lut, int64_t Lp,
                             const int32_t* gt_lut, int64_t Lg, int64_t* mat, mvp_stream_t stream);
 
+/* ---- stage one: test, validation and class weights from the frame store (NEW on the device) ----
+ * mvpnet/test_2d.py:103-118 and the validation pass of mvpnet/train_2d.py:240-312 (argmax of the 2D network's logits against the label
+ * frames), mvpnet/data/preprocess/compute_label_weights.py (np.bincount of the labels): raw 16-bit label frames through Pillow's
+ * NEAREST indices and the label mapping into integer counts, without the (Nf,h,w) int64 label tensor of mvp_prepare_labels_u16.
+ *
+ * The label arguments mean what they mean for mvp_prepare_labels_u16 (no flip): labels (Ftot,H,W) uint16; picked (Nf,) int64 global rows,
+ * clamped into [0, Ftot); yi (h) / xi (w) int32 ON THE DEVICE (mvp_resize_nearest_table), clamped into the image, NULL exactly when that
+ * axis keeps its size; mapping (T,) int64 on the device or NULL:
+ *     raw = labels[picked[f], yi[y], xi[x]];   label = mapping ? (raw < T ? mapping[raw] : ignore_value) : raw
+ *
+ * mvp_frame_confusion_f32: logit covers (Nf,C,h,w) float32, element (f,c,y,x) at logit[f*ld_f + c*ld_c + y*ld_y + x*ld_x] -- contiguous
+ *   NCHW, channels-last memory and a view with a padded ld_f go in as they lie.
+ *     am = the first maximum of the pixel's C logits: by strict `>` from class 0, as mvp_seg_confusion_f32 and torch.argmax.  NaN logits
+ *          are outside the contract (a NaN never wins a `>`: no fault, but not torch's answer).
+ *     mat (C,C) int64 += 1 at [label][am] for every pixel whose label lies in [0,C);
+ *     pred (Nf,h,w) int64 or NULL: am of EVERY pixel, ignored ones included.
+ *   labels and mat may both be NULL (an unlabelled split): then pred is required and only it is written; the label arguments are still
+ *   checked (pass H = h, W = w, Ftot = 1 and no tables), picked is not read.
+ *   One launch (per 65535 frames), one lane per output pixel, a 64-bit frame base and 32-bit offsets inside a frame; a pixel's logits
+ *   are read whether its label counts or not.  With ld_x == 1 the per-channel loads of a wave are contiguous; with ld_c == 1, C % 4 == 0, C <= 32 and 16-byte
+ *   aligned rows a lane reads its row in 16-byte loads.  A workgroup-private LDS histogram for C * C <= 4096 flushed with 64-bit integer atomics,
+ *   global integer atomics beyond: integer sums only, the same bits every run.  No allocation, no synchronisation (graph-capturable).
+ *   Before any launch: MVP_ENULL (logit; picked when labels and mat are given; pred when they are not); MVP_EINVAL for a size < 1 (Ftot, H,
+ *   W, h, w, C), Nf < 1, T < 0, a NULL table for a changed axis or a table for an unchanged one, labels without mat or mat without labels;
+ *   MVP_EUNSUPPORTED for C >= 2^16, H*W or h*w >= 2^31, or a logit frame whose extent (C-1)*ld_c + (h-1)*ld_y + (w-1)*ld_x reaches 2^30
+ *   elements (offsets inside a frame are 32-bit byte offsets); MVP_EINVAL for a negative stride.
+ *
+ * mvp_label_histogram_u16: hist (nbins,) int64 += 1 per pixel of the picked, resized frames whose label -- the mapped value, or the raw id
+ *   without a mapping; a raw id >= T counts nowhere -- lies in [0,nbins).  One launch (per 65535 frames), no label tensor.  An LDS histogram for
+ *   nbins <= 4096 (the 20 and 41 bins of the class weights), global integer atomics up to nbins = MVP_HISTOGRAM_MAX_BINS = 65536 (every raw
+ *   id).  MVP_ENULL (labels, picked, hist); MVP_EINVAL as above and for nbins < 1; MVP_EUNSUPPORTED for nbins > MVP_HISTOGRAM_MAX_BINS,
+ *   H*W or h*w >= 2^31.
+ * mvp_label_histogram_i64: label (n,) int64; hist (nbins,) int64 += 1 per value in [0,nbins): np.bincount(label, minlength) accumulated
+ *   (compute_3d_weights), negative and too large values dropped.  MVP_ENULL (label, hist); MVP_EINVAL unless n >= 0 and nbins >= 1;
+ *   MVP_EUNSUPPORTED for nbins > MVP_HISTOGRAM_MAX_BINS or n >= 2^40.  n == 0: nothing is launched. */
+#define MVP_HISTOGRAM_MAX_BINS 65536
+int mvp_frame_confusion_f32(const float* logit, int64_t Nf, int64_t C, int64_t h, int64_t w, int64_t ld_f, int64_t ld_c, int64_t ld_y,
+                            int64_t ld_x, const uint16_t* labels, int64_t Ftot, int64_t H, int64_t W, const int64_t* picked, const int32_t* yi,
+                            const int32_t* xi, const int64_t* mapping, int64_t T, int64_t ignore_value, int64_t* mat, int64_t* pred,
+                            mvp_stream_t stream);
+int mvp_label_histogram_u16(const uint16_t* labels, int64_t Ftot, int64_t H, int64_t W, const int64_t* picked, int64_t Nf, int64_t h,
+                            int64_t w, const int32_t* yi, const int32_t* xi, const int64_t* mapping, int64_t T, int64_t nbins, int64_t* hist,
+                            mvp_stream_t stream);
+int mvp_label_histogram_i64(const int64_t* label, int64_t n, int64_t nbins, int64_t* hist, mvp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

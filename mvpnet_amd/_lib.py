@@ -162,6 +162,9 @@ _SIGNATURES = {
     'mvp_resize_nearest_table': [_i64, _i64, _ptr],  # (host only: no stream)
     'mvp_resize_frames_u8': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
     'mvp_prepare_labels_u16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
+    'mvp_frame_confusion_f32': [_ptr] + [_i64] * 8 + [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr],
+    'mvp_label_histogram_u16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
+    'mvp_label_histogram_i64': [_ptr, _i64, _i64, _ptr, _ptr],
 }
 # the shared-MLP entry points with the precision as arguments (csrc/mlp_prec.hip): base parameters + (precision, precision_backward)
 for _n in ['mvp_mlp_forward_f32', 'mvp_mlp_forward_bn_f32', 'mvp_mlp_forward_rel_bn_f32', 'mvp_mlp_forward_pool_f32', 'mvp_mlp_input_grad_f32', 'mvp_mlp_input_grad_dropout_f32',

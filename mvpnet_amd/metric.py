@@ -3,6 +3,8 @@
   SegAccuracy, SegIoU           mvpnet/models/metric.py:5-73   (same names, `update_dict` contract, strings)
   Evaluator, CLASS_NAMES, ...   mvpnet/evaluate_3d.py:4-92     (confusion matrix + accuracy / IoU numbers only)
   DeviceEvaluator               the same for label tensors on the device (mvp_label_confusion_i64; nothing is read back until a number is)
+                                + update_frames: the 2D network's logits against raw label frames (mvp_frame_confusion_f32), mvpnet/test_2d.py
+  label_log_weights             mvpnet/data/preprocess/compute_label_weights.py (the arithmetic behind the class weights)
 
 MI355X side: for fp32 logits on the GPU both meters get `argmax -> mask by ignore_index -> bincount` from ONE pass of
 `mvp_seg_confusion_f32` over the logits where the network left them ((B,C,N) or channels-last rows); the reference runs
@@ -216,8 +218,9 @@ class DeviceEvaluator(object):
         for t in (pred_label, gt_label):
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise RuntimeError('DeviceEvaluator.update takes tensors on the GPU; use metric.Evaluator for host arrays')
-        if self._mat is None:
+        if self._lut is None:
             self._lut = self._host_lut.to(pred_label.device)
+        if self._mat is None:
             self._mat = torch.zeros((self.num_classes, self.num_classes), dtype=torch.int64, device=pred_label.device)
         pred, gt = pred_label.reshape(-1).long().contiguous(), gt_label.reshape(-1).long().contiguous()
         ops.label_confusion(pred, gt, self._mat, pred_lut=self._lut, gt_lut=self._lut)
@@ -227,6 +230,22 @@ class DeviceEvaluator(object):
             raise ValueError('one prediction array per ground-truth array expected')
         for p, g in zip(pred_labels, gt_labels):
             self.update(p, g)
+
+    def update_frames(self, seg_logit, labels, picked, *, size=None, mapping=None, want_pred=False):
+        """A batch of the 2D network's logits (Nf,C,h,w) against the frame store's raw label images, added to the running matrix: what
+        mvpnet/test_2d.py:113-118 does with `argmax(1).cpu().numpy()` and `batch_update` on host arrays.  Only launches
+        ops.frame_confusion (mvp_frame_confusion_f32: label read, mapping, argmax and count in one kernel); labels (Ftot,H,W) uint16,
+        picked, size, mapping as there.  Allowed when this evaluator's labels are arange(C), the `Evaluator(class_names)` of test_2d.py,
+        with C the logits' channel count: the class index is the position, so no table is needed; ValueError otherwise.
+        want_pred: -> the (Nf,h,w) int64 argmax of every pixel, written by the same launch."""
+        from . import ops
+        n = self.num_classes
+        if not np.array_equal(self.labels, np.arange(n)) or seg_logit.size(1) != n:
+            raise ValueError('DeviceEvaluator.update_frames: needs labels == arange(C) and C == seg_logit.size(1)')
+        if self._mat is None:  # (no table here: nothing is copied to the device)
+            self._mat = torch.zeros((n, n), dtype=torch.int64, device=seg_logit.device)
+        out = ops.frame_confusion(seg_logit, labels, picked, size=size, mapping=mapping, out=self._mat, want_pred=want_pred)
+        return out[1] if want_pred else None
 
     @property
     def confusion_matrix(self):
@@ -238,3 +257,27 @@ class DeviceEvaluator(object):
     class_seg_acc = Evaluator.class_seg_acc
     class_iou = Evaluator.class_iou
     overall_iou = Evaluator.overall_iou
+
+
+def summary_from_confusion(mat):
+    """{'seg_acc', 'seg_iou'} of a (C,C) int64 confusion matrix on the device (mvpnet2d.validate_2d's): the expressions of
+    SegAccuracy.global_avg and SegIoU.global_avg, so the numbers are the ones the two meters report after the same batches.  The read is
+    the only synchronisation."""
+    correct, valid = torch.stack([mat.diagonal().sum(), mat.sum()]).tolist()
+    h = mat.float()
+    tp = torch.diag(h)
+    return {'seg_acc': (0.0 + correct) / valid if valid else float('nan'), 'seg_iou': (tp / (h.sum(1) + h.sum(0) - tp)).mean().item()}
+
+
+def label_log_weights(hist, class_ids=None):
+    """The class weights `1 / log(1.2 + frequency)` that SegLoss is built with, from label counts (ops.label_histogram's, a tensor on the
+    device -- reading it is the only synchronisation -- or an array): the arithmetic of
+    mvpnet/data/preprocess/compute_label_weights.py:27-29 and :45-47, operation by operation.  The counts, taken at class_ids when given
+    (compute_3d_weights' VALID_CLASS_IDS = EVAL_CLASS_IDS), are cast to float32, divided by their float32 sum, and 1 / np.log(1.2 + w)
+    stays float32.  -> (len,) float32 NumPy array: what np.savetxt writes there and what SegLoss / config.build_loss_2d take as weights."""
+    counts = hist.cpu().numpy() if torch.is_tensor(hist) else np.asarray(hist)
+    label_weights = counts.astype(np.float64).astype(np.float32)
+    if class_ids is not None:
+        label_weights = label_weights[list(class_ids)]
+    label_weights = label_weights / np.sum(label_weights)
+    return 1 / np.log(1.2 + label_weights)

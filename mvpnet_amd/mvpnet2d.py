@@ -58,3 +58,97 @@ def train_step_2d(model, loss_fn, optimizer, data_batch, scheduler=None, max_gra
     if scheduler is not None:
         scheduler.step()
     return loss.detach(), preds
+
+
+def _eval_batches(who, store, frames, batch_size, resize):
+    """-> (frames (n,) int64 on the device, size = (w, h) or None when the store's size is kept, the batches as slices)"""
+    images = store['images']
+    labels = store.get('labels')
+    if images.dim() != 4 or (labels is not None and (labels.dim() != 3 or tuple(labels.shape) != tuple(images.shape[:3]))):
+        raise RuntimeError(who + ': images (Ftot,H,W,3) uint8 and labels (Ftot,H,W) uint16 must describe the same frames')
+    if int(batch_size) < 1:
+        raise RuntimeError(who + ': batch_size must be >= 1')
+    H, W = images.size(1), images.size(2)
+    if frames is None:
+        frames = torch.arange(images.size(0), dtype=torch.int64, device=images.device)
+    if frames.dim() != 1:
+        raise RuntimeError(who + ': frames must be (n,)')
+    size = None if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (W, H) else (int(resize[0]), int(resize[1]))
+    if frames.numel() < 1:
+        raise RuntimeError(who + ': no frames')
+    return frames, size, [slice(i, min(i + int(batch_size), frames.numel())) for i in range(0, frames.numel(), int(batch_size))]
+
+
+def _eval_images(images, picked, size, image_normalizer, channels_last):
+    """the images of scene.sample_train_batch_2d without an augmentation"""
+    from .scene import _arange
+    if size is None:
+        return ops.prepare_frames(images, picked, normalizer=image_normalizer, channels_last=channels_last)
+    small = ops.resize_frames(images, picked, size)
+    return ops.prepare_frames(small, _arange(picked.numel(), images.device), normalizer=image_normalizer, channels_last=channels_last)
+
+
+def test_frames_2d(model, store, frames=None, *, batch_size, resize=None, image_normalizer=None, label_mapping=None, channels_last=False,
+                   evaluator=None, want_pred=False):
+    """The loop of the reference's stage-one test (mvpnet/test_2d.py:103-118) from frames resident on the device, under torch.no_grad():
+    batches of `frames` in order, the last one partial (drop_last=False); per batch the images as scene.sample_train_batch_2d makes them
+    without an augmentation (resize -> `/ 255.` -> normalise), model({'image': ...})['seg_logit'], evaluator.update_frames -- the argmax,
+    the labels through Pillow's NEAREST indices and label_mapping, and the count in one launch.  No label tensor is made and nothing is
+    synchronised in the loop; the first number read from the evaluator is the synchronisation.  The model runs in eval mode (its mode is
+    restored afterwards).
+    store: images (Ftot,H,W,3) uint8 [, labels (Ftot,H,W) uint16]; frames (n,) int64 on the device or None for all; resize,
+    image_normalizer, label_mapping, channels_last: as scene.sample_train_batch_2d (config.build_batch_2d(cfg, training=False)).
+    evaluator: a metric.DeviceEvaluator to add to, a fresh `DeviceEvaluator(metric.CLASS_NAMES)` otherwise -- the network's class count
+    must be its.  -> the evaluator, or (evaluator, pred (n,h,w) int64) with want_pred.  A store without 'labels' (an unlabelled split)
+    gives (None, pred).  The command line, the logging and the table printing of the script are out of scope."""
+    from . import metric
+    frames, size, batches = _eval_batches('test_frames_2d', store, frames, batch_size, resize)
+    labels = store.get('labels')
+    if labels is not None and evaluator is None:
+        evaluator = metric.DeviceEvaluator(metric.CLASS_NAMES)
+    preds = []
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for part in batches:
+                picked = frames[part]
+                logit = model({'image': _eval_images(store['images'], picked, size, image_normalizer, channels_last)})['seg_logit']
+                if labels is None:
+                    preds.append(ops.frame_confusion(logit, None, None))
+                else:
+                    pred = evaluator.update_frames(logit, labels, picked, size=size, mapping=label_mapping, want_pred=want_pred)
+                    if want_pred:
+                        preds.append(pred)
+    finally:
+        model.train(was_training)
+    if labels is None:
+        return None, torch.cat(preds)
+    return (evaluator, torch.cat(preds)) if want_pred else evaluator
+
+
+def validate_2d(model, loss_fn, store, frames, *, batch_size, resize=None, image_normalizer=None, label_mapping=None, channels_last=False):
+    """The validation pass of the reference's stage-one training (mvpnet/train_2d.py:240-312) from frames resident on the device: the
+    model in eval mode (its mode is restored afterwards) under torch.no_grad(), batches of `frames` in order with the last one partial,
+    per batch loss_fn(preds, batch)['seg_loss'] and the confusion matrix.  SegLoss reads a label tensor, so the batch's labels are made
+    once with ops.prepare_labels and the matrix is taken from the same tensor (metric.confusion_matrix); nothing is synchronised.
+    -> {'loss': the mean of the per-batch losses (what the reference's loss meter reports as global_avg), a device scalar,
+        'confusion': (C,C) int64 on the device}; metric.summary_from_confusion turns the matrix into the seg_acc / seg_iou that
+    SegAccuracy and SegIoU report for the same batches.  Batch arguments: as test_frames_2d."""
+    from . import metric
+    frames, size, batches = _eval_batches('validate_2d', store, frames, batch_size, resize)
+    was_training = model.training
+    model.eval()
+    losses, mat = [], None
+    try:
+        with torch.no_grad():
+            for part in batches:
+                picked = frames[part]
+                batch = {'image': _eval_images(store['images'], picked, size, image_normalizer, channels_last),
+                         'seg_label': ops.prepare_labels(store['labels'], picked, size=size, mapping=label_mapping)}
+                preds = model(batch)
+                losses.append(loss_fn(preds, batch)['seg_loss'])
+                mat = metric.confusion_matrix(preds['seg_logit'], batch['seg_label'], out=mat)
+    finally:
+        model.train(was_training)
+    return {'loss': torch.stack(losses).mean(), 'confusion': mat}

@@ -8,6 +8,7 @@ import torch
 
 from . import chunks as CH
 from . import dist as D
+from . import metric
 from . import ops
 from .mvpnet3d import prefetch_geometry
 
@@ -785,3 +786,26 @@ def sample_train_batch_3d(store, scene_of_row, *, dataset, nb_pts, use_color=Fal
     if rot is not None:
         out['z_rot'] = rot
     return out
+
+
+def label_weights_2d(store, frames=None, *, resize=None, label_mapping, num_classes=20):
+    """The 2D class weights of mvpnet/data/preprocess/compute_label_weights.py:34-49 (`compute_2d_weights`) from label frames resident on
+    the device: one ops.label_histogram launch over `frames` -- (n,) int64 on the device, None for all; the reference takes every 100th
+    frame, `torch.arange(0, Ftot, 100)` -- at the YAML's resize (w, h) through label_mapping, then metric.label_log_weights on the counts
+    (the read of num_classes integers is the only synchronisation).  -> (num_classes,) float32 NumPy array, what the script saves."""
+    labels = store['labels']
+    size = None if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (labels.size(2), labels.size(1)) else (int(resize[0]), int(resize[1]))
+    return metric.label_log_weights(ops.label_histogram(labels, num_classes, picked=frames, size=size, mapping=label_mapping))
+
+
+def label_weights_3d(seg_label, *, num_labels=41, class_ids=tuple(metric.EVAL_CLASS_IDS)):
+    """The 3D class weights of compute_label_weights.py:16-31 (`compute_3d_weights`): seg_label -- the flat int64 label tensor of the 3D
+    store (raw nyu40 ids, as the script's pickle holds them) or a list of per-scene tensors, on the device -- counted into num_labels bins
+    (ops.label_histogram, one launch per tensor into one histogram), then metric.label_log_weights at class_ids (the default is the
+    script's VALID_CLASS_IDS; None: every bin).  -> (len(class_ids),) float32 NumPy array."""
+    hist = None
+    for t in ([seg_label] if torch.is_tensor(seg_label) else list(seg_label)):
+        hist = ops.label_histogram(t, num_labels, out=hist)
+    if hist is None:
+        raise RuntimeError('label_weights_3d: no labels')
+    return metric.label_log_weights(hist, class_ids)
