@@ -907,8 +907,9 @@ int mvp_mlp_layer_backward_wide_pooled_p_f32(const float* G, const float* Yi, co
  * tensor it writes.  For a first layer whose input needs no gradient (FeatureAggregation on a frozen 2D branch, mvpnet/models/mvpnet_3d.py:37-61)
  * nothing else needs dy.  X (R,ldx) plain (no activation prologue).  workspace / workspace_floats as mvp_mlp_weight_grad_ws_f32 (NULL / 0: fp32
  * atomics); precision arguments as every `_p_f32` entry point.  Supported: Cout % 4 == 0, 33 <= Cout, 16-byte aligned dZ / Y, and either Cin >= 33
- * on the split-bf16 kernel (1 or 2 backward pieces) or Cin <= 32 with 16-byte aligned rows on the fp32 kernel; MVP_EUNSUPPORTED otherwise (the
- * caller then runs the finish pass). */
+ * on the split-bf16 kernel (1 or 2 backward pieces) or Cin <= 32 with 16-byte aligned rows on the fp32 kernel -- the kernel of the fp32 precision
+ * and, under a split precision, of Cin < 8 only (8 <= Cin <= 32 under a split precision is refused); MVP_EUNSUPPORTED otherwise (the caller
+ * then runs the finish pass). */
 int mvp_mlp_weight_grad_finish_p_f32(const float* dZ, const float* Y, const float* mean, const float* invstd, const float* gamma, const double* stat,
                                      int training, const float* X, int64_t R, int64_t Cout, int64_t Cin, int64_t ldx, float* dW, int64_t lddw,
                                      float* workspace, int64_t workspace_floats, int precision, int precision_backward, mvp_stream_t stream);

@@ -1298,7 +1298,9 @@ MVP_API int mvp_mlp_weight_grad_ws_f32(const float* dY, const float* X, int64_t 
 // pass followed by mvp_mlp_weight_grad[_ws]_f32, without the pass and without the (R, Cout) tensor it writes.  For a FIRST layer whose input
 // needs no gradient (FeatureAggregation on a frozen 2D branch: mvpnet_3d.py:37-61) nothing else needs dy.  X without activation.
 // Cout a multiple of 4 with 33 <= Cout, 64-wide dY tiles; Cin >= 33 columns on the split-bf16 kernel (1 or 2 pieces), or Cin <= 32 on the
-// fp32 kernel (16-byte aligned rows); everything else: MVP_EUNSUPPORTED (callers run the finish pass).  workspace as mvp_mlp_weight_grad_ws_f32.
+// fp32 kernel (16-byte aligned rows) -- which weight_grad_impl takes under the fp32 precision, and under a split precision only for Cin < 8
+// (the four relation columns): 8 <= Cin <= 32 under a split precision stays on the split-bf16 kernel, whose finish form has 64-wide tiles
+// only, and is refused.  Everything else: MVP_EUNSUPPORTED (callers run the finish pass).  workspace as mvp_mlp_weight_grad_ws_f32.
 MVP_API int mvp_mlp_weight_grad_finish_p_f32(const float* dZ, const float* Y, const float* mean, const float* invstd, const float* gamma,
                                              const double* stat, int training, const float* X, int64_t R, int64_t Cout, int64_t Cin, int64_t ldx,
                                              float* dW, int64_t lddw, float* workspace, int64_t workspace_floats, int precision,
