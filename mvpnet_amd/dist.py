@@ -154,6 +154,7 @@ def vote_scene(logits, chunk_inds, n_pts):
     point ids per chunk.  Returns mean logits (n_pts, C), labels (n_pts,) with `count==0 -> C`,
     and the vote count -- the GPU restatement of mvpnet/test_mvpnet_3d.py:136-174."""
     from . import _lib as L
+    from .ops.vote import vote_finish
     C = logits.size(1)
     s = torch.zeros(n_pts, C, dtype=torch.float32, device=logits.device)
     cnt = torch.zeros(n_pts, dtype=torch.int32, device=logits.device)  # (no chunks: every point is "no prediction")
@@ -168,7 +169,4 @@ def vote_scene(logits, chunk_inds, n_pts):
             raise RuntimeError('vote_scene: a chunk lists {} points but its logits have {} columns'.format(plan['max_len'], logits.size(2)))
         L.call('mvp_vote_gather_f32', s, L.ptr(logits), logits.stride(0), logits.stride(2), logits.stride(1), L.ptr(plan['chunk_offsets']),
                len(chunk_inds), L.ptr(plan['pt_offsets']), L.ptr(plan['pt_slots']), n_pts, C, L.ptr(s), L.ptr(cnt))
-    mean = torch.empty_like(s)
-    label = torch.empty(n_pts, dtype=torch.int64, device=logits.device)
-    L.call('mvp_vote_finish_f32', s, L.ptr(s), L.ptr(cnt), n_pts, C, L.ptr(mean), L.ptr(label))
-    return mean, label, cnt
+    return (*vote_finish(s, cnt), cnt)

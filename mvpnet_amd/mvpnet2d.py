@@ -11,6 +11,8 @@ from torch import nn
 
 from . import ops
 from . import optim
+from .nn import eval_mode
+from .scene import _resize_target, _sized_frames
 
 
 class MVPNet2D(nn.Module):
@@ -68,24 +70,13 @@ def _eval_batches(who, store, frames, batch_size, resize):
         raise RuntimeError(who + ': images (Ftot,H,W,3) uint8 and labels (Ftot,H,W) uint16 must describe the same frames')
     if int(batch_size) < 1:
         raise RuntimeError(who + ': batch_size must be >= 1')
-    H, W = images.size(1), images.size(2)
     if frames is None:
         frames = torch.arange(images.size(0), dtype=torch.int64, device=images.device)
     if frames.dim() != 1:
         raise RuntimeError(who + ': frames must be (n,)')
-    size = None if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (W, H) else (int(resize[0]), int(resize[1]))
     if frames.numel() < 1:
         raise RuntimeError(who + ': no frames')
-    return frames, size, [slice(i, min(i + int(batch_size), frames.numel())) for i in range(0, frames.numel(), int(batch_size))]
-
-
-def _eval_images(images, picked, size, image_normalizer, channels_last):
-    """the images of scene.sample_train_batch_2d without an augmentation"""
-    from .scene import _arange
-    if size is None:
-        return ops.prepare_frames(images, picked, normalizer=image_normalizer, channels_last=channels_last)
-    small = ops.resize_frames(images, picked, size)
-    return ops.prepare_frames(small, _arange(picked.numel(), images.device), normalizer=image_normalizer, channels_last=channels_last)
+    return frames, _resize_target(resize, images.size(2), images.size(1)), [slice(i, min(i + int(batch_size), frames.numel())) for i in range(0, frames.numel(), int(batch_size))]
 
 
 def test_frames_2d(model, store, frames=None, *, batch_size, resize=None, image_normalizer=None, label_mapping=None, channels_last=False,
@@ -107,21 +98,17 @@ def test_frames_2d(model, store, frames=None, *, batch_size, resize=None, image_
     if labels is not None and evaluator is None:
         evaluator = metric.DeviceEvaluator(metric.CLASS_NAMES)
     preds = []
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for part in batches:
-                picked = frames[part]
-                logit = model({'image': _eval_images(store['images'], picked, size, image_normalizer, channels_last)})['seg_logit']
-                if labels is None:
-                    preds.append(ops.frame_confusion(logit, None, None))
-                else:
-                    pred = evaluator.update_frames(logit, labels, picked, size=size, mapping=label_mapping, want_pred=want_pred)
-                    if want_pred:
-                        preds.append(pred)
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for part in batches:
+            picked = frames[part]
+            image = _sized_frames(store['images'], picked, size, normalizer=image_normalizer, channels_last=channels_last)
+            logit = model({'image': image})['seg_logit']
+            if labels is None:
+                preds.append(ops.frame_confusion(logit, None, None))
+            else:
+                pred = evaluator.update_frames(logit, labels, picked, size=size, mapping=label_mapping, want_pred=want_pred)
+                if want_pred:
+                    preds.append(pred)
     if labels is None:
         return None, torch.cat(preds)
     return (evaluator, torch.cat(preds)) if want_pred else evaluator
@@ -137,18 +124,13 @@ def validate_2d(model, loss_fn, store, frames, *, batch_size, resize=None, image
     SegAccuracy and SegIoU report for the same batches.  Batch arguments: as test_frames_2d."""
     from . import metric
     frames, size, batches = _eval_batches('validate_2d', store, frames, batch_size, resize)
-    was_training = model.training
-    model.eval()
     losses, mat = [], None
-    try:
-        with torch.no_grad():
-            for part in batches:
-                picked = frames[part]
-                batch = {'image': _eval_images(store['images'], picked, size, image_normalizer, channels_last),
-                         'seg_label': ops.prepare_labels(store['labels'], picked, size=size, mapping=label_mapping)}
-                preds = model(batch)
-                losses.append(loss_fn(preds, batch)['seg_loss'])
-                mat = metric.confusion_matrix(preds['seg_logit'], batch['seg_label'], out=mat)
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for part in batches:
+            picked = frames[part]
+            batch = {'image': _sized_frames(store['images'], picked, size, normalizer=image_normalizer, channels_last=channels_last),
+                     'seg_label': ops.prepare_labels(store['labels'], picked, size=size, mapping=label_mapping)}
+            preds = model(batch)
+            losses.append(loss_fn(preds, batch)['seg_loss'])
+            mat = metric.confusion_matrix(preds['seg_logit'], batch['seg_label'], out=mat)
     return {'loss': torch.stack(losses).mean(), 'confusion': mat}

@@ -6,9 +6,23 @@ Same class names, constructor arguments and `state_dict` keys (`<i>.conv.weight`
 `<i>.bn.{weight,bias,running_mean,running_var,num_batches_tracked}`) so reference-trained
 checkpoints load.  The 1x1 convolutions themselves are PyTorch-ROCm plumbing here.
 """
+import contextlib
+
 import torch
 from torch import nn
 import torch.nn.functional as F
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """`model` in eval mode under torch.no_grad(); its mode is restored on the way out, also when the body raises."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        model.train(was_training)
 
 
 class _ConvBNReLU(nn.Module):

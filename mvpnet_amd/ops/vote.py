@@ -113,3 +113,12 @@ def lift_vote(logit, view_frame, knn, knn_base, chunk_inds, n_pts, plan=None):
            L.ptr(base), L.ptr(plan['chunk_offsets']), num_chunks, L.ptr(plan['pt_offsets']), L.ptr(plan['pt_slots']), n_pts, L.ptr(total),
            L.ptr(count))
     return total, count
+
+
+def vote_finish(total, count):
+    """The tail of every vote: total (n,C) float32 sums and count (n,) int32 votes -> (mean (n,C) = total / max(count, 1); label (n,) int64:
+    the first maximum, C where count is 0).  One launch (mvp_vote_finish_f32, pinned in include/mvp_hip.h)."""
+    mean = torch.empty_like(total)
+    label = torch.empty(total.size(0), dtype=torch.int64, device=total.device)
+    L.call('mvp_vote_finish_f32', total, L.ptr(total), L.ptr(count), total.size(0), total.size(1), L.ptr(mean), L.ptr(label))
+    return mean, label

@@ -11,6 +11,22 @@ from . import dist as D
 from . import metric
 from . import ops
 from .mvpnet3d import prefetch_geometry
+from .nn import eval_mode
+
+
+def _unwrap(model):
+    return model.module if hasattr(model, 'module') else model
+
+
+def _check_scene_points(who, points):
+    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32 or not points.is_cuda:
+        raise RuntimeError(who + ': points must be (n,3) float32 on the device')
+
+
+def _no_prediction(n_pts, num_classes, dev):
+    """What every whole-scene path returns for a scene without a kept window: zero logits, labels all `num_classes`, zero counts."""
+    return (torch.zeros((n_pts, num_classes), dtype=torch.float32, device=dev), torch.full((n_pts,), num_classes, dtype=torch.int64, device=dev),
+            torch.zeros((n_pts,), dtype=torch.int32, device=dev))
 
 
 def pad_sparse_chunk(data, min_nb_pts=2048, generator=None):
@@ -29,7 +45,7 @@ def pad_sparse_chunk(data, min_nb_pts=2048, generator=None):
 
 
 def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_classes=None):
-    """model: MVPNet3D / PN2SSG in eval mode on this rank's GPU.
+    """model: MVPNet3D / PN2SSG on this rank's GPU; run in eval mode under no_grad, its mode is restored (also when a forward raises).
     chunk_batches: list of data dicts (the reference's keys, tensors on the device) holding THIS RANK's chunks in the order
         `dist.shard_chunks(num_chunks, rank, world)`, any batch sizes.  Chunks may have DIFFERENT numbers of points (the
         reference feeds every chunk with all its points, `nb_pts=-1`, padded to >= 2048: pad_sparse_chunk): every batch holds
@@ -40,14 +56,11 @@ def infer_scene(model, chunk_batches, chunk_inds, n_pts, num_chunks=None, num_cl
     n_pts: number of scene points.
     Returns mean logits (n_pts, C), labels (n_pts,) with C = "no prediction" where a point is in no chunk, vote counts."""
     num_chunks = len(chunk_inds) if num_chunks is None else num_chunks
-    was_training = model.training
-    model.eval()
-    net = model.module if hasattr(model, 'module') else model
-    net3d = getattr(net, 'net_3d', net)
     if num_classes is None:
-        num_classes = int(net3d.num_classes)
-    outs = _forward_batches(model, chunk_batches)
-    model.train(was_training)
+        net = _unwrap(model)
+        num_classes = int(getattr(net, 'net_3d', net).num_classes)
+    with eval_mode(model):
+        outs = _forward_batches(model, chunk_batches)
     return _vote_chunk_logits(outs, chunk_inds, n_pts, num_chunks, num_classes)
 
 
@@ -57,7 +70,7 @@ def _forward_batches(model, chunk_batches, ready=None):
     hangs the run's feature store in there); the planning reads `points` only, so it never waits for it."""
     ready = ready or (lambda i, b: b)
     outs = []
-    net = model.module if hasattr(model, 'module') else model
+    net = _unwrap(model)
     net3d = getattr(net, 'net_3d', net)
     clouds = sum(b['points'].size(0) for b in chunk_batches)
     same_n = len({b['points'].size(2) for b in chunk_batches}) <= 1
@@ -117,8 +130,6 @@ def infer_scene_votes(model, points, feature=None, nb_pts=32768, num_votes=3, vo
     -> mean logits (n,C), labels (n,) -- every point gets one, this path has no "no prediction" class --, vote_inds (V,nb_pts).
     The propagation is ops.vote_nearest (nearest by float32 distance, lowest index on ties, votes added in order), the division by the
     number of votes and the argmax are mvp_vote_finish_f32."""
-    from . import _lib as L
-    from . import ops
     dev = points.device
     n = points.size(0)
     if points.dim() != 2 or points.size(1) != 3 or n < 1:
@@ -148,19 +159,10 @@ def infer_scene_votes(model, points, feature=None, nb_pts=32768, num_votes=3, vo
     batch = {'points': keys.transpose(1, 2).contiguous()}
     if feature is not None:
         batch['feature'] = feature[vote_inds].transpose(1, 2).contiguous()
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            logit = model(batch)['seg_logit']  # (V,C,nb), PN2SSG: a transposed view of row-major rows
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        logit = model(batch)['seg_logit']  # (V,C,nb), PN2SSG: a transposed view of row-major rows
     total = ops.vote_nearest(points.contiguous(), keys, logit)
-    count = torch.full((n,), V, dtype=torch.int32, device=dev)
-    mean = torch.empty_like(total)
-    label = torch.empty(n, dtype=torch.int64, device=dev)
-    L.call('mvp_vote_finish_f32', total, L.ptr(total), L.ptr(count), n, total.size(1), L.ptr(mean), L.ptr(label))
-    return mean, label, vote_inds
+    return (*ops.vote_finish(total, torch.full((n,), V, dtype=torch.int32, device=dev)), vote_inds)
 
 
 def prepare_scene(points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
@@ -228,17 +230,24 @@ def _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chu
 
 def _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, who, k, image_normalizer=None, channels_last=False):
     """-> batch(sel, points, pixel_box): one batch of a scene, the frames `sel` (B,nv) beside the chunks' points (B,3,N) and pixel boxes (B,4).
-    The frames come from the lifting-resolution depth maps and the intrinsics scaled to them with their inverse (scannet_2d3d.py:206-210,
-    :38), per frame, on the device."""
-    ldepth, cam, kinv = _scene_cameras(dev, depth, cam_matrix, images, lift_depth, who, image_normalizer, channels_last)
-    return lambda sel, points, pixel_box: {**_picked_views(images, ldepth, pose, sel, image_normalizer, channels_last), 'points': points,
-                                           'cam_matrix': cam[sel].contiguous(), 'kinv': kinv[sel].contiguous(),
-                                           'pixel_box': pixel_box.contiguous(), 'k': int(k)}
+    _scene_geometry's batch with `images` (B,nv,3,H,W) as the 2D network reads them."""
+    _, geometry = _scene_geometry(dev, depth, cam_matrix, pose, images, lift_depth, who, k, image_normalizer, channels_last)
+    return lambda sel, points, pixel_box: dict(geometry(sel, points, pixel_box), images=_test_frames(images, sel, image_normalizer, channels_last))
 
 
-def _scene_cameras(dev, depth, cam_matrix, images, lift_depth, who, image_normalizer=None, channels_last=False):
-    """-> (the lifting-resolution depth maps (F,H,W), cam (F,3,3), kinv (F,3,3)): the intrinsics scaled to those maps and their inverse
-    (scannet_2d3d.py:206-210, :38), per frame, on the device; `who` refuses images that disagree with the maps."""
+def _test_frames(images, sel, image_normalizer, channels_last):
+    """The frames `sel` (any shape, int64 on the device) as the 2D network reads them at test time: raw (F,H,W,3) uint8 frames through
+    ops.prepare_frames, float images -- final, the caller has asked _raw_frames -- by a plain gather."""
+    if images.dtype == torch.uint8:
+        return ops.prepare_frames(images, sel.contiguous(), normalizer=image_normalizer, channels_last=channels_last)
+    return images[sel].contiguous()
+
+
+def _scene_geometry(dev, depth, cam_matrix, pose, images, lift_depth, who, k, image_normalizer=None, channels_last=False):
+    """-> (the lifting-resolution depth maps (F,H,W); geometry(sel, points, pixel_box): one batch of a scene without its images -- depth,
+    pose, cam_matrix and kinv of the frames `sel` (B,nv) beside points, pixel_box and k).  The frames come from the lifting-resolution
+    depth maps and the intrinsics scaled to them with their inverse (scannet_2d3d.py:206-210, :38), per frame, on the device; `who`
+    refuses images that disagree with the maps."""
     import numpy as np
     ldepth = depth if lift_depth is None else lift_depth
     F, H, W = ldepth.shape
@@ -249,7 +258,10 @@ def _scene_cameras(dev, depth, cam_matrix, images, lift_depth, who, image_normal
     cam[..., 0, :] /= np.float32(depth.size(2) / W)  # `cam_matrix[0] /= resize_scale[0]` (:208-210)
     cam[..., 1, :] /= np.float32(depth.size(1) / H)
     kinv = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(cam))).to(dev).expand(F, 3, 3)  # float32, :38
-    return ldepth, torch.from_numpy(cam).to(dev).expand(F, 3, 3), kinv
+    cam = torch.from_numpy(cam).to(dev).expand(F, 3, 3)
+    return ldepth, lambda sel, points, pixel_box: {'depth': ldepth[sel].contiguous(), 'pose': pose[sel].contiguous(), 'points': points,
+                                                   'cam_matrix': cam[sel].contiguous(), 'kinv': kinv[sel].contiguous(),
+                                                   'pixel_box': pixel_box.contiguous(), 'k': int(k)}
 
 
 def _raw_frames(who, images, **given):
@@ -332,8 +344,8 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
     lengths, n_pts, dev = csr['lengths'], points.size(0), points.device
     if not lengths:
         return [], [], n_pts, []
-    batches, order, rows, picked, pixel_box = _bucketed_rows(csr, points, 'prepare_scene_bucketed', min_nb_pts, batch_size, max_batch_points, max_bucket,
-                                                             pad_seed)
+    batches, order, rows, picked, pixel_box, _ = _bucketed_rows(csr, points, 'prepare_scene_bucketed', min_nb_pts, batch_size, max_batch_points,
+                                                                max_bucket, pad_seed)
     batch = _scene_batcher(dev, depth, cam_matrix, pose, images, lift_depth, 'prepare_scene_bucketed', k, image_normalizer, channels_last)
     chunk_batches, lo = [], 0
     for (N, members), pts in zip(batches, rows):
@@ -345,14 +357,14 @@ def prepare_scene_bucketed(points, depth, cam_matrix, pose, images, *, chunk_siz
 
 
 def _bucketed_rows(csr, points, who, min_nb_pts, batch_size, max_batch_points, max_bucket, pad_seed):
-    """What prepare_scene_bucketed and infer_scene_shared share behind _scene_chunks: plan_buckets and ONE ops.pack_chunks launch.
-    -> (batches, order: plan_buckets' result; rows: every batch's padded points (B,3,N), views of one buffer; picked (C,nv) and pixel_box
-    (C,4) in the batches' order)."""
+    """What prepare_scene_bucketed, infer_scene_shared and infer_scene_2d share behind _scene_chunks: plan_buckets and ONE ops.pack_chunks
+    launch.  -> (batches, order: plan_buckets' result; rows: every batch's padded points (B,3,N), views of one buffer; picked (C,nv) and
+    pixel_box (C,4) in the batches' order; slot_base: _bucket_slots', the row of each chunk's first point, in the chunker's numbering)."""
     lengths = csr['lengths']
     batches, order, slot_base, out_len = _bucket_slots(lengths, who, min_nb_pts, batch_size, max_batch_points, max_bucket)
     packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, [3 * s for s in slot_base], out_len, seed=pad_seed)
     order_t = torch.tensor(order, dtype=torch.int64).to(points.device)
-    return batches, order, _batch_views(packed, 3, batches, slot_base), csr['picked'][order_t], csr['pixel_box'][order_t]
+    return batches, order, _batch_views(packed, 3, batches, slot_base), csr['picked'][order_t], csr['pixel_box'][order_t], slot_base
 
 
 def _bucket_slots(lengths, who, min_nb_pts, batch_size, max_batch_points, max_bucket):
@@ -392,9 +404,8 @@ def infer_scene_3d(model, points, colors=None, *, chunk_size=(1.5, 1.5), chunk_s
     batch's points and features, _forward_batches, _vote_chunk_logits (the atomics-free vote, adding in the batches' order).
     -> mean logits (n,C), labels (n,) with C where no chunk holds the point, counts (n,) int32.  A scene with no kept window gives zeros,
     labels all C and counts zero, and nothing goes through the model."""
-    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32 or not points.is_cuda:
-        raise RuntimeError('infer_scene_3d: points must be (n,3) float32 on the device')
-    net = model.module if hasattr(model, 'module') else model
+    _check_scene_points('infer_scene_3d', points)
+    net = _unwrap(model)
     dev, n_pts, num_classes = points.device, points.size(0), int(net.num_classes)
     use_color = (getattr(net, 'in_channels', 0) == 3) if use_color is None else bool(use_color)
     source = {}
@@ -407,20 +418,15 @@ def infer_scene_3d(model, points, colors=None, *, chunk_size=(1.5, 1.5), chunk_s
     csr = CH.scene2chunks_csr(points, chunk_size, chunk_stride, thresh=chunk_thresh, margin=chunk_margin)
     lengths = csr['lengths']
     if not lengths:
-        return (torch.zeros((n_pts, num_classes), dtype=torch.float32, device=dev), torch.full((n_pts,), num_classes, dtype=torch.int64, device=dev),
-                torch.zeros((n_pts,), dtype=torch.int32, device=dev))
+        return _no_prediction(n_pts, num_classes, dev)
     batches, order, slot_base, out_len = _bucket_slots(lengths, 'infer_scene_3d', min_nb_pts, batch_size, max_batch_points, max_bucket)
     flat_points, flat_feature = ops.pack_cloud(points.contiguous(), csr['index'], csr['offsets'], lengths, slot_base, out_len, seed=pad_seed, **source)
     chunk_batches = [{'points': p} for p in _batch_views(flat_points, 3, batches, slot_base)]
     if use_color:
         for b, f in zip(chunk_batches, _batch_views(flat_feature, 3, batches, slot_base)):
             b['feature'] = f
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         outs = _forward_batches(model, chunk_batches)
-    finally:
-        model.train(was_training)
     chunk_inds = torch.split(csr['index'], lengths)
     return _vote_chunk_logits(outs, [chunk_inds[c] for c in order], n_pts, len(order), num_classes)
 
@@ -456,6 +462,36 @@ def plan_store_groups(frames_of_batch, max_frames):
     return runs
 
 
+def _frames_through(net_2d, key, images, image_normalizer, channels_last):
+    """-> run(frames): the frames (b,) int64 on the device, as the 2D network reads them (_test_frames), through net_2d -> its `key` output."""
+    return lambda frames: net_2d({'image': _test_frames(images, frames, image_normalizer, channels_last)})[key]
+
+
+def _frame_store(distinct, F, H, W, frame_batch, run, who, dev, channels=None):
+    """Every distinct picked frame through the 2D network once (infer_scene_shared per run, infer_scene_2d per scene).  distinct: the
+    frames, an ascending host list of ints in [0, F); run(frames (b,) int64 on `dev`) -> (b,C,H,W) float32, called with at most frame_batch
+    frames at a time; channels: C, or None = the first output's.  `who` refuses any other output.
+    -> (store (U,H,W,C) float32 -- channels-last memory whatever the network writes: the copy into the store makes a pixel's C values one
+    contiguous row, and store.permute(0, 3, 1, 2) is the (U,C,H,W) tensor --, slot_of (F,) int32: a frame's place in the store, -1 for a
+    frame that is not in it)."""
+    frames = torch.tensor(distinct, dtype=torch.int64).to(dev)
+    store = None
+    for lo in range(0, len(distinct), int(frame_batch)):
+        part = frames[lo:lo + int(frame_batch)]
+        out = run(part)
+        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float32 \
+                or tuple(out.shape) != (part.numel(), out.size(1) if channels is None else channels, H, W):
+            raise RuntimeError('{}: net_2d must return a float32 (b,{},{},{}) tensor for b frames: the lifting maps\' size'.format(
+                who, 'C' if channels is None else channels, H, W))
+        if store is None:
+            channels = out.size(1)
+            store = torch.empty((len(distinct), H, W, channels), dtype=torch.float32, device=dev)
+        store[lo:lo + part.numel()].permute(0, 3, 1, 2).copy_(out)
+    slot_of = torch.full((F,), -1, dtype=torch.int32, device=dev)
+    slot_of[frames] = torch.arange(len(distinct), dtype=torch.int32, device=dev)
+    return store, slot_of
+
+
 def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                        min_nb_pts=2048, overlap=None, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None, pad_seed=0, batch_size=32,
                        max_batch_points=32 * 8192, max_bucket=32768, image_normalizer=None, channels_last=False, frame_batch=32,
@@ -476,70 +512,45 @@ def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_
     store is released before the next run's is made.  A frame two runs share runs once per run.
     -> mean logits (n_pts,C), labels (n_pts,) with C where no chunk holds the point, counts (n_pts,) int32, as infer_scene.  A scene with
     no kept window gives zeros, labels all C, counts zero, and nothing goes through the 2D network."""
-    dev, n_pts, nv = points.device, points.size(0), int(num_rgbd_frames)
+    dev, n_pts = points.device, points.size(0)
     if frame_batch < 1:
         raise RuntimeError('infer_scene_shared: frame_batch must be at least 1')
-    net = model.module if hasattr(model, 'module') else model
-    net_2d, num_classes, C = net.net_2d, int(net.net_3d.num_classes), int(net.feat_aggreg.in_channels)
+    net = _unwrap(model)
+    num_classes, C = int(net.net_3d.num_classes), int(net.feat_aggreg.in_channels)
     csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
                         num_base_pts, radius, generator)
     lengths = csr['lengths']
     if not lengths:
-        return (torch.zeros((n_pts, num_classes), dtype=torch.float32, device=dev), torch.full((n_pts,), num_classes, dtype=torch.int64, device=dev),
-                torch.zeros((n_pts,), dtype=torch.int32, device=dev))
-    ldepth, cam, kinv = _scene_cameras(dev, depth, cam_matrix, images, lift_depth, 'infer_scene_shared', image_normalizer, channels_last)
+        return _no_prediction(n_pts, num_classes, dev)
+    ldepth, geometry = _scene_geometry(dev, depth, cam_matrix, pose, images, lift_depth, 'infer_scene_shared', k, image_normalizer, channels_last)
     F, H, W = ldepth.shape
-    batches, order, rows, picked, pixel_box = _bucketed_rows(csr, points, 'infer_scene_shared', min_nb_pts, batch_size, max_batch_points, max_bucket,
-                                                             pad_seed)
+    batches, order, rows, picked, pixel_box, _ = _bucketed_rows(csr, points, 'infer_scene_shared', min_nb_pts, batch_size, max_batch_points, max_bucket,
+                                                                pad_seed)
     picked_host = picked.cpu().tolist()  # (the one read)
     chunk_batches, sels, frames_of_batch, lo = [], [], [], 0
     for (_, members), pts in zip(batches, rows):  # prepare_scene_bucketed's batches without `images`
         hi = lo + len(members)
-        sel = picked[lo:hi]
-        chunk_batches.append({'depth': ldepth[sel].contiguous(), 'pose': pose[sel].contiguous(), 'points': pts, 'cam_matrix': cam[sel].contiguous(),
-                              'kinv': kinv[sel].contiguous(), 'pixel_box': pixel_box[lo:hi].contiguous(), 'k': int(k)})
-        sels.append(sel)
+        chunk_batches.append(geometry(picked[lo:hi], pts, pixel_box[lo:hi]))
+        sels.append(picked[lo:hi])
         frames_of_batch.append({f for row in picked_host[lo:hi] for f in row})
         lo = hi
     runs = plan_store_groups(frames_of_batch, int(max_store_bytes) // (H * W * C * 4))
     run_of_batch = {first: r for r, (first, _, _) in enumerate(runs)}
+    run_2d = _frames_through(net.net_2d, 'feature', images, image_normalizer, channels_last)
     state = {'store': None, 'slot_of': None}
-
-    def run_2d(frames):  # (b,) int64 on the device -> (b,C,H,W)
-        if images.dtype == torch.uint8:
-            x = ops.prepare_frames(images, frames, normalizer=image_normalizer, channels_last=channels_last)
-        else:
-            x = images[frames].contiguous()
-        out = net_2d({'image': x})['feature']
-        if not torch.is_tensor(out) or out.dim() != 4 or tuple(out.shape) != (frames.numel(), C, H, W) or out.dtype != torch.float32:
-            raise RuntimeError('infer_scene_shared: net_2d must return float32 feature (b,{},{},{}): the aggregation\'s channels at the lifting '
-                               'maps\' size'.format(C, H, W))
-        return out
 
     def ready(i, batch):
         """Batch i as the model takes it; the first batch of a run makes the run's store (the previous one is released first)."""
         if i in run_of_batch:
-            distinct = runs[run_of_batch[i]][2]
             state['store'] = state['slot_of'] = None
-            frames = torch.tensor(distinct, dtype=torch.int64).to(dev)
-            # channels-last memory whatever the network writes: the copy into the store makes a neighbour's C features one contiguous row
-            store = torch.empty((len(distinct), H, W, C), dtype=torch.float32, device=dev)
-            for lo in range(0, len(distinct), int(frame_batch)):
-                out = run_2d(frames[lo:lo + int(frame_batch)])
-                store[lo:lo + out.size(0)].permute(0, 3, 1, 2).copy_(out)
-            slot_of = torch.full((F,), -1, dtype=torch.int32, device=dev)
-            slot_of[frames] = torch.arange(len(distinct), dtype=torch.int32, device=dev)
-            state['store'], state['slot_of'] = store, slot_of
+            state['store'], state['slot_of'] = _frame_store(runs[run_of_batch[i]][2], F, H, W, frame_batch, run_2d, 'infer_scene_shared', dev, C)
         return dict(batch, feature_store=state['store'], view_slot=state['slot_of'][sels[i]].contiguous())
 
-    was_training = model.training
-    model.eval()
     try:
-        with torch.no_grad():
+        with eval_mode(model):
             outs = _forward_batches(model, chunk_batches, ready)
     finally:
         state.clear()
-        model.train(was_training)
     chunk_inds = torch.split(csr['index'], lengths)
     return _vote_chunk_logits(outs, [chunk_inds[c] for c in order], n_pts, len(order), num_classes)
 
@@ -555,109 +566,62 @@ def infer_scene_2d(model, points, depth, cam_matrix, pose, images, *, chunk_size
 
     The reference feeds the chunks one by one, each with its own num_rgbd_frames frames, so the 2D network sees a frame once per chunk
     that picked it.  In eval mode a frame's logits do not depend on its batch neighbours: here the network runs ONCE per distinct picked
-    frame and writes into one channels-last logit store; the pixel k-NN runs per chunk against that chunk's own views and box, in
-    size-bucketed batches (plan_buckets with min_nb_pts = 1: there is no FPS to pad for; the padded rows are searched and never read),
-    into one flat index buffer; ops.lift_vote then goes from every scene point through its chunk positions and their k pixel ids to the
-    logit rows in one launch, adding in the chunker's chunk order -- the reference's -- and mvp_vote_finish_f32 divides and labels.
-    One device-to-host read beyond _scene_chunks': the number of distinct picked frames.
+    frame and writes into one channels-last logit store (_frame_store, infer_scene_shared's); the pixel k-NN runs per chunk against that
+    chunk's own views and box, in size-bucketed batches (_bucketed_rows with min_nb_pts = 1: there is no FPS to pad for; the padded rows
+    are searched and never read), into one flat index buffer; ops.lift_vote then goes from every scene point through its chunk positions
+    and their k pixel ids to the logit rows in one launch, adding in the chunker's chunk order -- the reference's -- and ops.vote_finish
+    divides and labels.  One device-to-host read beyond _scene_chunks': the picked table, from which the host lists the distinct frames.
     -> mean logits (n_pts,C), labels (n_pts,) with C where no chunk holds the point, counts (n_pts,) int32.  A scene with no kept window
     gives zeros, labels all C and counts zero (C: net_2d.num_classes, else one frame is run to learn it)."""
-    from . import _lib as L
-    dev, n_pts = points.device, points.size(0)
+    n_pts = points.size(0)
     parts = _scene_2d_inputs(model, points, depth, cam_matrix, pose, images, chunk_size=chunk_size, chunk_stride=chunk_stride, chunk_thresh=chunk_thresh,
                              chunk_margin=chunk_margin, num_rgbd_frames=num_rgbd_frames, k=k, overlap=overlap, lift_depth=lift_depth,
                              num_base_pts=num_base_pts, radius=radius, generator=generator, image_normalizer=image_normalizer,
                              channels_last=channels_last, frame_batch=frame_batch)
-    C = parts['num_classes']
     if 'logit' not in parts:
-        return (torch.zeros((n_pts, C), dtype=torch.float32, device=dev), torch.full((n_pts,), C, dtype=torch.int64, device=dev),
-                torch.zeros((n_pts,), dtype=torch.int32, device=dev))
+        return _no_prediction(n_pts, parts['num_classes'], points.device)
     total, count = ops.lift_vote(parts['logit'], parts['view_frame'], parts['knn'], parts['knn_base'], parts['chunk_inds'], n_pts)
-    mean = torch.empty_like(total)
-    label = torch.empty(n_pts, dtype=torch.int64, device=dev)
-    L.call('mvp_vote_finish_f32', total, L.ptr(total), L.ptr(count), n_pts, C, L.ptr(mean), L.ptr(label))
-    return mean, label, count
+    return (*ops.vote_finish(total, count), count)
 
 
 def _scene_2d_inputs(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                      overlap, lift_depth, num_base_pts, radius, generator, image_normalizer, channels_last, frame_batch):
     """infer_scene_2d up to the vote: -> {'num_classes'} for a scene without a kept window, else what ops.lift_vote takes -- logit (U,C,H,W)
-    in channels-last memory: the store of the distinct picked frames' logits; view_frame (num_chunks,nv) int32; knn (R,k) int64 and
-    knn_base: the chunks' rows, batch after batch; chunk_inds in the chunker's order -- and picked (num_chunks,nv)."""
+    in channels-last memory: _frame_store's store of the distinct picked frames' logits; view_frame (num_chunks,nv) int32: its slot_of at
+    the picked table; knn (R,k) int64 and knn_base: the chunks' rows, batch after batch (_bucketed_rows' placement); chunk_inds in the
+    chunker's order -- and picked (num_chunks,nv).  The picked table is read to the host once, for the distinct frames."""
     from . import _lib as L
     dev, nv, k = points.device, int(num_rgbd_frames), int(k)
-    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32 or not points.is_cuda:
-        raise RuntimeError('infer_scene_2d: points must be (n,3) float32 on the device')
+    _check_scene_points('infer_scene_2d', points)
     if not 1 <= k <= ops.vote.MAX_K or frame_batch < 1:
         raise RuntimeError('infer_scene_2d: needs 1 <= k <= {} and frame_batch >= 1'.format(ops.vote.MAX_K))
-    ldepth, cam, kinv = _scene_cameras(dev, depth, cam_matrix, images, lift_depth, 'infer_scene_2d', image_normalizer, channels_last)
+    ldepth, geometry = _scene_geometry(dev, depth, cam_matrix, pose, images, lift_depth, 'infer_scene_2d', k, image_normalizer, channels_last)
     F, H, W = ldepth.shape
-    net = model.module if hasattr(model, 'module') else model
-    net_2d = net.net_2d
-
-    def run_2d(frames):  # (b,) int64 on the device -> (b,C,H,W)
-        if images.dtype == torch.uint8:
-            x = ops.prepare_frames(images, frames, normalizer=image_normalizer, channels_last=channels_last)
-        else:
-            x = images[frames].contiguous()
-        return net_2d({'image': x})['seg_logit']
-
+    net_2d = _unwrap(model).net_2d
+    run_2d = _frames_through(net_2d, 'seg_logit', images, image_normalizer, channels_last)
     csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
                         num_base_pts, radius, generator)
     lengths = csr['lengths']
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            if not lengths:
-                C = getattr(net_2d, 'num_classes', None)
-                C = int(run_2d(torch.zeros(1, dtype=torch.int64, device=dev)).size(1)) if C is None else int(C)
-                return {'num_classes': C}
-            if min(lengths) < 1:
-                raise RuntimeError('infer_scene_2d: a chunk without points (chunk_thresh must be at least 1)')
-            # the distinct picked frames, ascending, and every view's place among them
-            picked = csr['picked']  # (num_chunks,nv) int64
-            present = torch.zeros(F, dtype=torch.bool, device=dev)
-            present[picked.reshape(-1)] = True
-            slot = torch.cumsum(present, 0) - 1
-            view_frame = slot[picked].to(torch.int32)
-            U = int(present.sum())  # (the one read)
-            distinct = torch.sort((~present).to(torch.uint8), stable=True).indices[:U]
-            store = None
-            for lo in range(0, U, int(frame_batch)):
-                out = run_2d(distinct[lo:lo + int(frame_batch)])
-                if store is None:
-                    if out.dim() != 4 or tuple(out.shape[2:]) != (H, W) or out.dtype != torch.float32:
-                        raise RuntimeError('infer_scene_2d: net_2d must return float32 seg_logit (F,C,{},{}), the lifting maps\' size'.format(H, W))
-                    # channels-last memory whatever the network writes: the copy into the store is needed anyway, and it makes a
-                    # neighbour's C logits one contiguous row
-                    store = torch.empty((U, H, W, out.size(1)), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
-                store[lo:lo + out.size(0)].copy_(out)
-            # pixel k-NN per chunk, in size-bucketed batches, into one flat buffer
-            batches, _ = plan_buckets(lengths, min_nb_pts=1)
-            out_base, out_len, knn_base, at, rows = [0] * len(lengths), [0] * len(lengths), [0] * len(lengths), 0, 0
-            for N, members in batches:
-                for c in members:
-                    out_base[c], out_len[c], knn_base[c], at, rows = at, N, rows, at + 3 * N, rows + N
-            packed = ops.pack_chunks(points.contiguous(), csr['index'], csr['offsets'], lengths, out_base, out_len)
-            knn = torch.empty((rows, k), dtype=torch.int64, device=dev)
-            order_t = torch.tensor([c for _, members in batches for c in members], dtype=torch.int64).to(dev)
-            sel_all, box_all = picked[order_t], csr['pixel_box'][order_t]
-            pose, lo = pose.contiguous(), 0
-            for N, members in batches:
-                B, first = len(members), out_base[members[0]]
-                sel = sel_all[lo:lo + B]
-                pts = packed[first:first + B * 3 * N].view(B, 3, N).transpose(1, 2).contiguous()
-                bcam, bpose = cam[sel].contiguous(), pose[sel].contiguous()
-                xyz, mask = ops.unproject(ldepth[sel].contiguous(), kinv[sel].contiguous(), bpose, box_all[lo:lo + B].contiguous())
-                mask = mask.to(torch.uint8)
-                L.call('mvp_pixel_knn_projective_f32', pts, L.ptr(xyz), L.ptr(mask), L.ptr(pts), L.ptr(bcam), L.ptr(bpose), B, nv, H, W, N, k,
-                       L.ptr_at(knn, knn_base[members[0]] * k), None)
-                lo += B
-            return {'logit': store, 'view_frame': view_frame, 'knn': knn, 'knn_base': knn_base, 'chunk_inds': list(torch.split(csr['index'], lengths)),
-                    'picked': picked, 'num_classes': int(store.size(1))}
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        if not lengths:
+            C = getattr(net_2d, 'num_classes', None)
+            return {'num_classes': int(run_2d(torch.zeros(1, dtype=torch.int64, device=dev)).size(1)) if C is None else int(C)}
+        # pixel k-NN per chunk, in size-bucketed batches (no FPS to pad for: min_nb_pts = 1), into one flat buffer
+        batches, _, rows, picked, pixel_box, knn_base = _bucketed_rows(csr, points, 'infer_scene_2d', 1, 32, 32 * 8192, 32768, 0)
+        distinct = sorted({f for row in csr['picked'].cpu().tolist() for f in row})  # (the one read)
+        store, slot_of = _frame_store(distinct, F, H, W, frame_batch, run_2d, 'infer_scene_2d', dev)
+        knn = torch.empty((sum(N * len(members) for N, members in batches), k), dtype=torch.int64, device=dev)
+        lo = 0
+        for (N, members), pts in zip(batches, rows):
+            B, pts = len(members), pts.transpose(1, 2).contiguous()  # (B,N,3)
+            d = geometry(picked[lo:lo + B], pts, pixel_box[lo:lo + B])
+            xyz, mask = ops.unproject(d['depth'], d['kinv'], d['pose'], d['pixel_box'])
+            mask = mask.to(torch.uint8)
+            L.call('mvp_pixel_knn_projective_f32', pts, L.ptr(xyz), L.ptr(mask), L.ptr(pts), L.ptr(d['cam_matrix']), L.ptr(d['pose']), B, nv, H, W, N, k,
+                   L.ptr_at(knn, knn_base[members[0]] * k), None)
+            lo += B
+        return {'logit': store.permute(0, 3, 1, 2), 'view_frame': slot_of[csr['picked']], 'knn': knn, 'knn_base': knn_base,
+                'chunk_inds': list(torch.split(csr['index'], lengths)), 'picked': csr['picked'], 'num_classes': int(store.size(3))}
 
 
 def sample_train_batch(store, scene_of_chunk, *, nb_pts, num_rgbd_frames, k, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2), chunk_thresh=0.3,
@@ -727,18 +691,27 @@ def sample_train_batch_2d(store, picked, *, resize=None, color_jitter=(), image_
         raise RuntimeError('sample_train_batch_2d: images (Ftot,H,W,3) uint8 and labels (Ftot,H,W) uint16 must describe the same frames')
     if picked.dim() != 1:
         raise RuntimeError('sample_train_batch_2d: picked must be (B,)')
-    H, W = images.size(1), images.size(2)
-    size = None if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (W, H) else (int(resize[0]), int(resize[1]))
+    size = _resize_target(resize, images.size(2), images.size(1))
     dev, B = images.device, picked.numel()
     factor, order = A.draw_color_jitter(B, color_jitter, dev, generator=generator) if color_jitter else (None, None)
     flips = A.draw_flip(B, flip, dev, generator=generator) if flip else None
-    if size is None:
-        image = ops.prepare_frames(images, picked, factor=factor, order=order, flip=flips, normalizer=image_normalizer, channels_last=channels_last)
-    else:
-        small = ops.resize_frames(images, picked, size)
-        image = ops.prepare_frames(small, _arange(B, dev), factor=factor, order=order, flip=flips, normalizer=image_normalizer,
-                                   channels_last=channels_last)
+    image = _sized_frames(images, picked, size, factor=factor, order=order, flip=flips, normalizer=image_normalizer, channels_last=channels_last)
     return {'image': image, 'seg_label': ops.prepare_labels(labels, picked, size=size, flip=flips, mapping=label_mapping)}
+
+
+def _resize_target(resize, W, H):
+    """The YAML's resize (w, h) -> the size to resize (W,H) frames to, or None when there is nothing to do: no resize, or the frames' own."""
+    if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (W, H):
+        return None
+    return int(resize[0]), int(resize[1])
+
+
+def _sized_frames(images, picked, size, *, factor=None, order=None, flip=None, normalizer, channels_last):
+    """The frames `picked` (B,) of a raw (Ftot,H,W,3) uint8 store as the 2D network reads them: ops.resize_frames to `size` (_resize_target's)
+    when it is not None, then ops.prepare_frames with the given jitter, flip and normaliser."""
+    if size is not None:
+        images, picked = ops.resize_frames(images, picked, size), _arange(picked.numel(), images.device)
+    return ops.prepare_frames(images, picked, factor=factor, order=order, flip=flip, normalizer=normalizer, channels_last=channels_last)
 
 
 _ARANGE = {}  # (device, n) -> arange(n) int64 on the device: made once, so a later batch launches nothing for it
@@ -794,7 +767,7 @@ def label_weights_2d(store, frames=None, *, resize=None, label_mapping, num_clas
     frame, `torch.arange(0, Ftot, 100)` -- at the YAML's resize (w, h) through label_mapping, then metric.label_log_weights on the counts
     (the read of num_classes integers is the only synchronisation).  -> (num_classes,) float32 NumPy array, what the script saves."""
     labels = store['labels']
-    size = None if resize is None or len(resize) == 0 or (int(resize[0]), int(resize[1])) == (labels.size(2), labels.size(1)) else (int(resize[0]), int(resize[1]))
+    size = _resize_target(resize, labels.size(2), labels.size(1))
     return metric.label_log_weights(ops.label_histogram(labels, num_classes, picked=frames, size=size, mapping=label_mapping))
 
 
