@@ -1216,6 +1216,27 @@ int mvp_seg_loss_backward_f32(const float* logit, int64_t B, int64_t C, int64_t 
                               mvp_stream_t stream);
 int mvp_seg_confusion_f32(const float* logit, int64_t B, int64_t C, int64_t N, int64_t ld_b, int64_t ld_c, int64_t ld_n,
                           const int64_t* label, int64_t ignore_index, int64_t* mat, mvp_stream_t stream);
+/* mvp_seg_loss_meter_f32: mvp_seg_loss_f32 and the meters of a training iteration (mvpnet/train_mvpnet_3d.py:170-173: SegAccuracy,
+ *   SegIoU, the loss meter) in ONE launch, with the meter state resident on the device.  logit .. loss: as mvp_seg_loss_f32 -- the same
+ *   row arithmetic and workgroup partition, acc[0..2] and *loss are what that entry point leaves (mvp_seg_loss_backward_f32 takes the acc);
+ *   acc == NULL && loss == NULL is the meters-only form (no loss is formed; the loss slots below get a NaN); exactly one of the two NULL:
+ *   MVP_ENULL.  The state is owned by the caller and ZEROED once (construction / reset), never per call; W = window, 1 <= W <= 64:
+ *     meter_i64, MVP_SEG_METER_I64(C, W) int64: [0] u, the number of updates; [1] correct, [2] valid: cumulative counts of the valid points
+ *       (argmax == label / all); [3] the launch's ticket, back at 0 when the launch ends; [4 + 2 s], [5 + 2 s], s = 0 .. W: a ring of the
+ *       (correct, valid) pairs as they stood after update s (mod W + 1) -- slot 0 is the zero state before the first update --, so the
+ *       counts of the last k = min(u, W) updates are cumulative - ring[(u - k) % (W + 1)], in exact integers; then the running (C,C)
+ *       matrix mat[label][argmax] (first maximum, as mvp_seg_confusion_f32).
+ *     meter_f64, MVP_SEG_METER_F64(W) float64: [0] the sum of the per-update losses (added in update order); [1 + j % W]: the float32 loss
+ *       of update j, the last W of them.
+ *   The LAST workgroup of the launch takes the cumulative pair, increments u and writes the two ring slots: the cursor lives on the
+ *   device, so every launch has the same arguments and may sit in a captured graph.  Launches that share a state must be ordered (one
+ *   stream).  Errors: a NULL pointer (weight excepted) is MVP_ENULL ahead of any other error; window or sizes out of range MVP_EINVAL. */
+#define MVP_SEG_METER_MAX_WINDOW 64
+#define MVP_SEG_METER_I64(C, W) (4 + 2 * ((W) + 1) + (C) * (C))
+#define MVP_SEG_METER_F64(W) (1 + (W))
+int mvp_seg_loss_meter_f32(const float* logit, int64_t B, int64_t C, int64_t N, int64_t ld_b, int64_t ld_c, int64_t ld_n,
+                           const int64_t* label, const float* weight, int64_t ignore_index, double* acc, float* loss,
+                           int64_t* meter_i64, double* meter_f64, int64_t window, mvp_stream_t stream);
 
 /* ---- scene results: the model ensemble and the evaluator's confusion matrix (NEW on the device) ----
  * mvp_ensemble_softmax_f32: mvpnet/ensemble.py:45-49 -- `sum_m scipy.special.softmax(logit_m, axis=1)`, then argmax -- in ONE launch.

@@ -205,6 +205,15 @@ def build_batch_2d(cfg, training=True):
             'color_jitter': tuple(float(v) for v in jitter) if jitter else (), 'flip': float(aug.get('flip', 0.0))}
 
 
+def build_val(cfg):
+    """The YAML's VAL node (common/config/base.py, all three tasks) as what the validation pass takes: batch_size and repeats for
+    scene.val_batches (VAL.BATCH_SIZE, VAL.REPEATS: mvpnet/data/build.py:28-47), period -- validate every so many iterations and at the
+    last one, 0 = never (train_mvpnet_3d.py:105-106,221) --, metric -- the meter whose global average selects the best checkpoint
+    (VAL.METRIC: mvpnet3d.is_better)."""
+    val = cfg.VAL
+    return {'batch_size': int(val.BATCH_SIZE), 'repeats': int(val.get('REPEATS', 1)), 'period': int(val.PERIOD), 'metric': str(val.METRIC)}
+
+
 def scannet_label_mapping(tsv_path, labelids_path, ignore_value=-100):
     """The `raw_to_scannet` table of mvpnet/data/scannet_2d.py:86-103 as a (T,) int64 tensor (on the host: move it to the store's device
     once): raw ScanNet id -> nyu40 id (the columns `id` and `nyu40id` of scannetv2-labels.combined.tsv, ids the file does not list -> 0)

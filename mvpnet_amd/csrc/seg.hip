@@ -323,6 +323,181 @@ __global__ __launch_bounds__(kST) void seg_confusion_kernel(const float* __restr
       if (hist[i]) atomicAdd(mat + i, (unsigned long long)hist[i]);
 }
 
+// ---- loss + the meters of a training iteration in one launch (mvp_seg_loss_meter_f32) -------------------------------------------------
+// seg_loss_kernel with the argmax and the confusion count taken from the row it already holds, and the meter state (include/mvp_hip.h)
+// updated by the launch's last workgroup.  The loss half KEEPS seg_loss_kernel's row arithmetic (row_lse / regs_lse on the same values)
+// and its workgroup partition (same grid, same rows per lane in the same order), so acc[0], acc[1] are fp64 sums of the same workgroup
+// partials and the loss is the same float32 to within one ulp (tests/test_meters_gpu.py derives the bound from exactly this).
+struct SegMeter {
+  unsigned int* hist;        // the workgroup's (C,C) counts in LDS, or nullptr: straight to mat
+  unsigned long long* mat;
+  int C;
+  unsigned int ok = 0u, valid = 0u;  // this lane's rows (at most R / 256 < 2^32)
+  __device__ __forceinline__ void count(int y, int am) {
+    if (hist)
+      atomicAdd(&hist[y * C + am], 1u);
+    else
+      atomicAdd(mat + (int64_t)y * C + am, 1ull);
+    valid += 1u;
+    ok += am == y ? 1u : 0u;
+  }
+};
+
+// first maximum of x[0 .. C): strict `>` from class 0, as seg_confusion_kernel and torch.argmax
+template <int CMAX>
+__device__ __forceinline__ int regs_argmax(const float* x, int C) {
+  float mx = x[0];
+  int am = 0;
+#pragma unroll
+  for (int c = 1; c < CMAX; ++c)
+    if (c < C && x[c] > mx) {
+      mx = x[c];
+      am = c;
+    }
+  return am;
+}
+
+template <int Q>
+__device__ __forceinline__ void seg_loss_meter_rows(const float* __restrict__ logit, int64_t R, const int64_t* __restrict__ label,
+                                                    const float* __restrict__ weight, int64_t ignore_index, bool want_loss, float4* tile,
+                                                    double& s_nll, double& s_w, SegMeter& meter) {
+  constexpr int C = 4 * Q;
+  for (int64_t base = (int64_t)blockIdx.x * kST; base < R; base += (int64_t)gridDim.x * kST) {
+    const int64_t r = base + threadIdx.x;
+    const int64_t y = r < R ? label[r] : -1;
+    float x[C], mx;
+    seg_load_rows<Q>(logit, base + (threadIdx.x & ~(kWave - 1)), R, tile, x);
+    if (r >= R || y == ignore_index || y < 0 || y >= C) continue;
+    meter.count((int)y, regs_argmax<C>(x, C));
+    if (!want_loss) continue;
+    const float lse = regs_lse<Q>(x, &mx);
+    float xy = x[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) xy = c == (int)y ? x[c] : xy;
+    const float nll = (mx + lse) - xy;
+    const float w = weight ? weight[y] : 1.f;
+    s_nll += (double)(w * nll);
+    s_w += (double)w;
+  }
+}
+
+__global__ __launch_bounds__(kST) void seg_loss_meter_kernel(const float* __restrict__ logit, int64_t B, int C, int64_t N, int64_t ld_b,
+                                                             int64_t ld_c, int64_t ld_n, const int64_t* __restrict__ label,
+                                                             const float* __restrict__ weight, int64_t ignore_index, double* __restrict__ acc,
+                                                             float* __restrict__ loss, unsigned long long* __restrict__ mi,
+                                                             double* __restrict__ mf, int W) {
+  __shared__ double red[kST / kWave];
+  __shared__ SegTile tile[kST / kWave];
+  __shared__ unsigned int hist[kMaxHist];
+  __shared__ unsigned long long wg_count[2];
+  const int64_t R = B * N;
+  const bool want_loss = acc != nullptr;
+  // workgroup-private histogram as in seg_confusion_kernel; below 2^32 rows no 32-bit bin can wrap
+  const bool lds = C * C <= kMaxHist && R < (1ll << 32);
+  unsigned long long* mat = mi + 4 + 2 * (W + 1);
+  if (lds)
+    for (int i = threadIdx.x; i < C * C; i += kST) hist[i] = 0u;
+  if (threadIdx.x < 2) wg_count[threadIdx.x] = 0ull;
+  __syncthreads();
+  SegMeter meter{lds ? hist : nullptr, mat, C};
+  double s_nll = 0.0, s_w = 0.0;
+  if (seg_rows_layout(logit, B, C, N, ld_b, ld_c, ld_n)) {
+#define SEG_CALL(Q) seg_loss_meter_rows<Q>(logit, R, label, weight, ignore_index, want_loss, tile[threadIdx.x >> 6], s_nll, s_w, meter)
+    SEG_ROWS_DISPATCH(C, SEG_CALL)
+#undef SEG_CALL
+  } else  // any other layout: one row per lane at its strides
+  for (int64_t r = (int64_t)blockIdx.x * kST + threadIdx.x; r < R; r += (int64_t)gridDim.x * kST) {
+    const int64_t y = label[r];
+    if (y == ignore_index || y < 0 || y >= C) continue;
+    const int64_t b = r / N, n = r - b * N;
+    const float* p = logit + b * ld_b + n * ld_n;
+    float mx, x[kRegC];
+    if (C <= kRegC) {
+      const float lse = row_lse(p, ld_c, C, &mx, x);  // (the meters-only form pays for the exponentials here: it is not the hot layout)
+      meter.count((int)y, regs_argmax<kRegC>(x, C));
+      if (!want_loss) continue;
+      const float nll = (mx + lse) - p[y * ld_c];
+      const float w = weight ? weight[y] : 1.f;
+      s_nll += (double)(w * nll);
+      s_w += (double)w;
+    } else {
+      float top = p[0];
+      int am = 0;
+      for (int c = 1; c < C; ++c) {
+        const float v = p[(int64_t)c * ld_c];
+        if (v > top) {
+          top = v;
+          am = c;
+        }
+      }
+      meter.count((int)y, am);
+      if (!want_loss) continue;
+      const float lse = row_lse(p, ld_c, C, &mx, x);
+      const float nll = (mx + lse) - p[y * ld_c];
+      const float w = weight ? weight[y] : 1.f;
+      s_nll += (double)(w * nll);
+      s_w += (double)w;
+    }
+  }
+  // the lanes' counts: one LDS atomic per wave, one pair of global atomics per workgroup
+  unsigned int ok = meter.ok, valid = meter.valid;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    ok += __shfl_xor(ok, m, kWave);
+    valid += __shfl_xor(valid, m, kWave);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    atomicAdd(&wg_count[0], (unsigned long long)ok);
+    atomicAdd(&wg_count[1], (unsigned long long)valid);
+  }
+  const double t0 = block_sum(s_nll, red);  // (its barriers also close the histogram and the two counts)
+  const double t1 = block_sum(s_w, red);
+  // The histogram goes out through waves 1 .. 3: up to 256 workgroups add to the same C * C words, those adds queue, and wave 0's
+  // completion wait below must not stand in that queue (nothing in this launch reads the matrix: the kernel's end publishes it).
+  if (lds && threadIdx.x >= kWave)
+    for (int i = threadIdx.x - kWave; i < C * C; i += kST - kWave)
+      if (hist[i]) atomicAdd(mat + i, (unsigned long long)hist[i]);
+  if (threadIdx.x == 0) {
+    if (want_loss) {
+      atomicAdd(acc + 0, t0);
+      atomicAdd(acc + 1, t1);
+    }
+    atomicAdd(mi + 1, wg_count[0]);
+    atomicAdd(mi + 2, wg_count[1]);
+    // as in seg_loss_kernel: this lane's device-scope atomics are complete before the ticket is drawn -- a completion wait, not a fence
+    wait_vm_complete();
+    const unsigned long long ticket = atomicAdd(mi + 3, 1ull);
+    if (ticket == (unsigned long long)gridDim.x - 1) {
+      // every workgroup's sums and counts have landed.  Nothing else touches the cursor, the rings or the ticket during the launch.
+      // The words the adds went to are read with device-scope atomic LOADS (coherent at device scope like the adds; the compiler
+      // itself turns an integer `atomicAdd(p, 0)` into one): read-modify-write atomics are bracketed and waited for one by one, a trip
+      // to the memory side each (measured: +3.9 us for five of them on a 17 us launch), the loads are in flight together.
+      double a0 = 0.0, a1 = 0.0;
+      if (want_loss) {
+        a0 = __hip_atomic_load(acc + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        a1 = __hip_atomic_load(acc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      const unsigned long long c = __hip_atomic_load(mi + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long v = __hip_atomic_load(mi + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long u = __hip_atomic_load(mi + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
+      const double sum = __hip_atomic_load(mf + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      float l = __builtin_nanf("");
+      if (want_loss) {
+        l = (float)(a0 / a1);  // no valid point: 0/0 = nan, as torch
+        *loss = l;
+        reinterpret_cast<unsigned long long*>(acc)[2] = (unsigned long long)gridDim.x;  // what seg_loss_kernel's ticket ends at
+      }
+      unsigned long long* snap = mi + 4 + 2 * (u % (unsigned long long)(W + 1));
+      snap[0] = c;
+      snap[1] = v;
+      mf[1 + u % (unsigned long long)W] = (double)l;
+      mf[0] = sum + (double)l;
+      __hip_atomic_store(mi + 0, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(mi + 3, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the ticket resets itself: no zero fill per call
+    }
+  }
+}
+
 int check_seg(const float* logit, int64_t B, int64_t C, int64_t N, const int64_t* label) {
   MVP_NONNULL(logit);
   MVP_NONNULL(label);
@@ -345,6 +520,26 @@ MVP_API int mvp_seg_loss_f32(const float* logit, int64_t B, int64_t C, int64_t N
   const unsigned blocks = (unsigned)std::min<int64_t>(256, std::max<int64_t>(1, cdiv(R, kST)));
   hipLaunchKernelGGL(seg_loss_kernel, dim3(blocks), dim3(kST), 0, static_cast<hipStream_t>(stream), logit, B, (int)C, N, ld_b, ld_c, ld_n,
                      label, weight, ignore_index, acc, loss);
+  return mvp_launch_status();
+}
+
+MVP_API int mvp_seg_loss_meter_f32(const float* logit, int64_t B, int64_t C, int64_t N, int64_t ld_b, int64_t ld_c, int64_t ld_n,
+                                   const int64_t* label, const float* weight, int64_t ignore_index, double* acc, float* loss,
+                                   int64_t* meter_i64, double* meter_f64, int64_t window, mvp_stream_t stream) {
+  MVP_NONNULL(logit);  // every null ahead of any other error
+  MVP_NONNULL(label);
+  MVP_NONNULL(meter_i64);
+  MVP_NONNULL(meter_f64);
+  if ((acc == nullptr) != (loss == nullptr)) return MVP_ENULL;  // both: the loss as well; neither: the meters only
+  int rc = check_seg(logit, B, C, N, label);
+  if (rc) return rc;
+  MVP_REQUIRE(window >= 1 && window <= MVP_SEG_METER_MAX_WINDOW);
+  const int64_t R = B * N;
+  // mvp_seg_loss_f32's grid, for the reason written there (here five atomics per workgroup on two cache lines) -- and because the loss
+  // must be summed over the same workgroup partials
+  const unsigned blocks = (unsigned)std::min<int64_t>(256, std::max<int64_t>(1, cdiv(R, kST)));
+  hipLaunchKernelGGL(seg_loss_meter_kernel, dim3(blocks), dim3(kST), 0, static_cast<hipStream_t>(stream), logit, B, (int)C, N, ld_b, ld_c,
+                     ld_n, label, weight, ignore_index, acc, loss, reinterpret_cast<unsigned long long*>(meter_i64), meter_f64, (int)window);
   return mvp_launch_status();
 }
 

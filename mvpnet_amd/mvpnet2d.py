@@ -45,7 +45,8 @@ def train_step_2d(model, loss_fn, optimizer, data_batch, scheduler=None, max_gra
     zero_grad -> forward -> loss_fn(preds, batch)['seg_loss'] -> backward -> [clip] -> step -> scheduler; -> (loss.detach(), preds).
     With max_grad_norm > 0 and an optim.FusedSGD the clip is deferred: optim.total_grad_norm leaves its coefficient on the device and
     the step multiplies the gradients by it as it reads them -- they are read once for the norm, once in the step and never rewritten
-    (so p.grad holds the UNclipped gradients afterwards).  Any other optimizer gets optim.clip_grad_norm_, the in-place clip."""
+    (so p.grad holds the UNclipped gradients afterwards).  Any other optimizer gets optim.clip_grad_norm_, the in-place clip.
+    The iteration's meters (train_2d.py:174-177) ride on loss_fn: SegLoss(meters=metric.DeviceMeters(...)) updates them in the loss launch."""
     optimizer.zero_grad()
     preds = model(data_batch)
     loss = loss_fn(preds, data_batch)['seg_loss']

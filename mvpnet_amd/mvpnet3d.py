@@ -233,18 +233,45 @@ class _SegLossFn(torch.autograd.Function):
         return grad, None, None, None
 
 
+class _SegLossMeterFn(torch.autograd.Function):
+    """_SegLossFn with the meters of the iteration updated by the same launch (mvp_seg_loss_meter_f32: the loss sums, acc and the loss
+    scalar are mvp_seg_loss_f32's; metric.DeviceMeters holds the meter state).  The backward is _SegLossFn's, on the same acc."""
+
+    @staticmethod
+    def forward(ctx, logit, label, weight, ignore_index, meters):
+        L.require_gpu(label, weight)
+        acc = R.zero_pool.zeros(3, torch.float64, logit.device)  # [sum w*nll, sum w, ticket]
+        loss = torch.empty((), dtype=torch.float32, device=logit.device)
+        meters._launch(logit, label, weight, acc, loss)
+        ctx.save_for_backward(logit, label, weight, acc)
+        ctx.ignore_index = int(ignore_index)
+        _SegLossFn.last_acc = acc
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _SegLossFn.backward(ctx, grad_out) + (None,)
+
+
 class SegLoss(nn.Module):
     """Weighted cross entropy with ignore_index (loss.py:5-21).  fp32 (B,C,N) logits on the GPU go through the fused HIP
     kernels (logits in any strides), and so do the 2D stage's (B,C,H,W) logits with (B,H,W) labels, contiguous or channels-last: they
     are VIEWED as (B,C,H*W) -- both layouts merge H and W without a copy -- and the gradient comes back in the logits' own layout;
-    everything else (host tensors, other dtypes / ranks) through F.cross_entropy, which is what the reference calls."""
+    everything else (host tensors, other dtypes / ranks) through F.cross_entropy, which is what the reference calls.
+    meters: a metric.DeviceMeters (given here or set later as the attribute `meters`) -- on the fused path the forward is then ONE launch
+    that also updates the iteration's meters (SegAccuracy, SegIoU, the loss meter: train_mvpnet_3d.py:170-173) on the device, in training
+    and under no_grad alike, with nothing read back; the backward is unchanged.  On the F.cross_entropy path `meters.update_dict` follows
+    the loss (it refuses what its kernel cannot take).  The meters' class count and ignore_index must be this loss's.  None: no meters."""
 
-    def __init__(self, weight=None, ignore_index=-100):
+    def __init__(self, weight=None, ignore_index=-100, meters=None):
         super().__init__()
         self.weight, self.ignore_index = weight, ignore_index
         self.last_weight_sum = None  # sum of w[label] over the valid points of the last call (0-dim tensor): dist.GradSync(weight_sum=)
+        self.meters = meters
 
     def forward(self, preds, labels):
+        if self.meters is not None:
+            return self._forward_meters(preds, labels, self.meters)
         logit, label = preds['seg_logit'], labels['seg_label']
         if logit.is_cuda and logit.dtype == torch.float32 and logit.dim() == 4 and label.dim() == 3 and label.dtype == torch.int64:
             # (B,C,H,W) -> (B,C,H*W): a view for contiguous and channels-last memory alike (stride(H) == W * stride(W))
@@ -259,6 +286,27 @@ class SegLoss(nn.Module):
                 valid = label != self.ignore_index
                 self.last_weight_sum = (valid.sum().to(logit.dtype) if self.weight is None
                                         else self.weight.to(logit.device)[label[valid]].sum())
+        return {'seg_loss': loss}
+
+    def _forward_meters(self, preds, labels, meters):
+        source, label = preds['seg_logit'], labels['seg_label']
+        if meters.ignore_index != self.ignore_index:
+            raise ValueError('SegLoss: the meters ignore {}, the loss ignores {}'.format(meters.ignore_index, self.ignore_index))
+        fused = source.is_cuda and source.dtype == torch.float32 and label.dtype == torch.int64 and \
+            ((source.dim() == 4 and label.dim() == 3) or source.dim() == 3)
+        if not fused:
+            self.meters = None
+            try:
+                out = self.forward(preds, labels)
+            finally:
+                self.meters = meters
+            meters.update_dict(preds, labels)
+            return out
+        logit, label = meters._operands(source, label)  # the (B,C,N) view and contiguous labels; ValueError before any launch
+        weight = None if self.weight is None else self.weight.to(device=logit.device, dtype=torch.float32).contiguous()
+        loss = _SegLossMeterFn.apply(logit, label, weight, self.ignore_index, meters)
+        meters._counted(source)
+        self.last_weight_sum = _SegLossFn.last_acc[1] if _SegLossFn.last_acc is not None else None
         return {'seg_loss': loss}
 
 
@@ -348,7 +396,9 @@ def train_step(model, loss_fn, optimizer, data_batch, scheduler=None, max_grad_n
     next_batch: the batch of the NEXT iteration (already on the device); its geometry is prefetched.
     marks: a callable(name) invoked at 'begin', 'fwd_end' (loss enqueued), 'bwd_begin' (just before loss.backward()), 'bwd_first' (from a
     hook on the logits' gradient: the first backward kernel is enqueued), 'bwd_end', 'end' -- a measurement aid (bench.py records HIP
-    events on the training stream there: where the stream waits for the host shows up as time between two marks)."""
+    events on the training stream there: where the stream waits for the host shows up as time between two marks).
+    The iteration's meters (:170-173) need nothing here: they ride on loss_fn -- SegLoss(meters=metric.DeviceMeters(...)) updates them
+    in the loss launch, without a host synchronisation."""
     if marks is not None:
         marks('begin')
     optimizer.zero_grad()
@@ -382,6 +432,53 @@ def train_step(model, loss_fn, optimizer, data_batch, scheduler=None, max_grad_n
     if marks is not None:
         marks('end')
     return loss.detach(), preds
+
+
+def validate(model, loss_fn, batches, meters=None):
+    """The validation pass of stage two and of the 3D baselines (mvpnet/train_mvpnet_3d.py:221-284, train_3d.py) over batches that are
+    on the device already: model and loss_fn in eval mode under torch.no_grad() -- every module's training flag is put back afterwards,
+    also when the body raises --, per batch the forward and loss_fn with `meters` attached (whatever loss_fn.meters was is re-attached
+    afterwards), so the loss, the accuracy counts and the confusion matrix of a batch are ONE launch and nothing is synchronised in the
+    loop.  The geometry of the batch after the current one is started (prefetch_geometry) before the current forward.
+    batches: any iterable of batch dicts -- MVPNet3D's (scene.sample_train_batch) or the baselines' (scene.sample_train_batch_3d), e.g.
+    a generator over scene.val_batches.  meters: a metric.DeviceMeters to continue; None makes a fresh one for the logits' class count
+    and loss_fn.ignore_index.  -> the DeviceMeters (None when `batches` is empty and none was given): summary() reads the numbers the
+    reference logs, meters()[i].global_avg is what VAL.METRIC selects (is_better)."""
+    from . import metric
+    flags = [(m, m.training) for m in list(model.modules()) + list(loss_fn.modules())]
+    had = getattr(loss_fn, 'meters', None)
+    model.eval()
+    loss_fn.eval()
+    try:
+        with torch.no_grad():
+            it = iter(batches)
+            cur = next(it, None)
+            while cur is not None:
+                nxt = next(it, None)
+                if nxt is not None:
+                    prefetch_geometry(model, nxt)  # (a model without a 3D geometry plan, or a batch that carries one: nothing to do)
+                preds = model(cur)
+                if meters is None:
+                    meters = metric.DeviceMeters(preds['seg_logit'].size(1), ignore_index=getattr(loss_fn, 'ignore_index', -100))
+                loss_fn.meters = meters
+                loss_fn(preds, cur)
+                cur = nxt
+    finally:
+        loss_fn.meters = had
+        for m, flag in flags:
+            m.training = flag
+    return meters
+
+
+def is_better(metric_name, cur, best):
+    """The best-checkpoint rule of train_mvpnet_3d.py:275-277: is the validation value `cur` of VAL.METRIC better than `best`?  None always
+    loses (no best yet: anything is better; no current value: nothing is); a name that contains 'loss' is better when lower, everything
+    else when higher."""
+    if cur is None:
+        return False
+    if best is None:
+        return True
+    return cur < best if 'loss' in metric_name else cur > best
 
 
 def _plan_tensors(plan):
@@ -440,7 +537,11 @@ class GraphedTrainStep:
 
     step(batch, next_batch) copies the two batches into the static input tensors (keys of the reference's data dict; the 2D
     feature map is produced inside the graph by model.net_2d) and replays.  Batches must arrive in sequence: `batch` of call
-    i is `next_batch` of call i-1, as with train_step(..., next_batch=...)."""
+    i is `next_batch` of call i-1, as with train_step(..., next_batch=...).
+
+    The iteration's meters ride on loss_fn (SegLoss(meters=metric.DeviceMeters(...))): their update is part of the captured loss launch --
+    the window cursor lives on the device, so every replay advances it -- and nothing here changes for them.  The eager warm-up
+    iterations of the constructor update them too: reset() the meters after building the step, and read() them after replays."""
 
     COPY_KEYS = ('images', 'points', 'seg_label', 'depth', 'cam_matrix', 'kinv', 'pose', 'pixel_box', 'image_xyz', 'knn_indices', 'flip', 'z_rot')
 

@@ -761,6 +761,22 @@ def sample_train_batch_3d(store, scene_of_row, *, dataset, nb_pts, use_color=Fal
     return out
 
 
+def val_batches(num_scenes, *, batch_size, repeats, sample, device):
+    """The validation loader of stage two and of the 3D baselines (mvpnet/data/build.py:28-47) as a generator: the order of
+    RepeatSampler (common/utils/sampler.py:36-45: range(num_scenes), `repeats` times over, VAL.REPEATS) cut into batches of `batch_size`
+    with the last one partial (drop_last=False), each handed to `sample` as a (b,) int64 tensor on `device` -- the dataset indices of
+    the batch, what scene.sample_train_batch / sample_train_batch_3d take as scene_of_chunk / scene_of_row.  `sample` is the caller's
+    closure over one of the two with the validation recipe (no flip, jitter or rotation; the baselines' VAL.AUGMENTATION CropPad is
+    sample_train_batch_3d's nb_pts); what it returns is yielded.  The whole order is ONE host-to-device copy, made before the first batch; mvpnet3d.validate consumes the
+    generator one batch ahead."""
+    num_scenes, batch_size, repeats = int(num_scenes), int(batch_size), int(repeats)
+    if num_scenes < 0 or batch_size < 1 or repeats < 0:
+        raise ValueError('val_batches: num_scenes >= 0, batch_size >= 1, repeats >= 0 expected')
+    order = torch.arange(num_scenes, dtype=torch.int64).repeat(repeats).to(device)
+    for lo in range(0, order.numel(), batch_size):
+        yield sample(order[lo:lo + batch_size])
+
+
 def label_weights_2d(store, frames=None, *, resize=None, label_mapping, num_classes=20):
     """The 2D class weights of mvpnet/data/preprocess/compute_label_weights.py:34-49 (`compute_2d_weights`) from label frames resident on
     the device: one ops.label_histogram launch over `frames` -- (n,) int64 on the device, None for all; the reference takes every 100th
