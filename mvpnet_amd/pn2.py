@@ -56,6 +56,17 @@ def _has_hooks(module):
     return any(m._forward_hooks or m._forward_pre_hooks for m in module.modules())
 
 
+def _run_forward_hooks(module, inputs, output):
+    """The forward hooks of a module whose work ran through the rows kernels instead of module.__call__ (PN2SSG.mlp_seg): each gets
+    (module, inputs, output) in the rows layout and may replace the output, as nn.Module.__call__ has it."""
+    with_kwargs = getattr(module, '_forward_hooks_with_kwargs', {})
+    for key, hook in list(module._forward_hooks.items()):
+        res = hook(module, inputs, {}, output) if key in with_kwargs else hook(module, inputs, output)
+        if res is not None:
+            output = res
+    return output
+
+
 class QueryGrouper(nn.Module):
     """Ball query + grouping around centroids (modules.py:13-41)."""
 
@@ -644,7 +655,10 @@ class PN2SSG(nn.Module):
             up = fp(xyzs[-2 - level], xyzs[-1 - level], feats[-2 - level], up, rows=True, geometry=geo, sparse_act=hand, act_out=nxt)
             hand = nxt
         if x is None:
-            x = R.shared_mlp_rows(up.reshape(B * N, -1), self.mlp_seg, dropout_p=self.mlp_seg.p, training=self.training)
+            up = up.reshape(B * N, -1)
+            x = R.shared_mlp_rows(up, self.mlp_seg, dropout_p=self.mlp_seg.p, training=self.training)
+            if self.mlp_seg._forward_hooks:  # (a watched head is never merged, see above: its watchers get the head's own rows)
+                x = _run_forward_hooks(self.mlp_seg, (up,), x)
         logit = R.linear_rows(x, self.seg_logit.weight, self.seg_logit.bias, act_src=head_hand)  # (B*N, classes)
         # (B,classes,N) as the reference returns it -- as a transposed VIEW of the rows: the loss and the vote kernels take strided logits,
         # the gradient comes back in the same layout (mvpnet3d._SegLossFn), so neither direction pays a transposing copy
