@@ -703,6 +703,8 @@ int mvp_sa_fused_forward_f32(const float* zf, const float* xyz, const float* cen
  * Layers with max(Cin, Cout) < min_width keep the fp32 MFMA.  Returns MVP_EINVAL for other values. */
 int mvp_set_mlp_precision(int terms, int min_width);
 int mvp_get_mlp_precision(void);
+/* min_width of the last mvp_set_mlp_precision (0 until then): what a host that routes layers between entry points has to agree with */
+int mvp_get_mlp_min_width(void);
 /* Split of the gradient contractions (dW, input gradient, mvp_mlp_layer_backward_f32) while the forward precision is a split one:
  * terms = 3 (default), 6 or 1. */
 int mvp_set_mlp_precision_backward(int terms);

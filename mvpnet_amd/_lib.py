@@ -5,6 +5,7 @@ the call raises.  PyTorch is only used for device memory and streams.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -13,179 +14,59 @@ LIB_PATH = os.environ.get('MVP_LIBRARY') or os.path.join(_HERE, 'libmvp_hip.so')
 _lib = None
 MLP_PRECISIONS = {'fp32': 0, 'bf16': 1, 'bf16x3': 3, 'bf16x6': 6}
 
-_i64 = ctypes.c_int64
-_ptr = ctypes.c_void_p
-_f32 = ctypes.c_float
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'mvp_hip.h')
 
-# name -> argtypes (restype is always int); mirrors include/mvp_hip.h one to one
-_SIGNATURES = {
-    'mvp_fps_f32': [_ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_fps_f64': [_ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_fps_shape_f32': [_ptr, _i64, _i64, _i64, _i64, _ptr, ctypes.c_int, _ptr],
-    'mvp_fps_shape_f64': [_ptr, _i64, _i64, _i64, _i64, _ptr, ctypes.c_int, _ptr],
-    'mvp_fps_checked_f32': [_ptr, _i64, _i64, _i64, _i64, _ptr, ctypes.c_int, _ptr, _ptr],
-    'mvp_fps_centroid_levels_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_ball_query_f32': [_ptr, _ptr, _i64, _i64, _i64, _f32, _i64, _ptr, _ptr],
-    'mvp_ball_query_f64': [_ptr, _ptr, _i64, _i64, _i64, _f32, _i64, _ptr, _ptr],
-    'mvp_ball_query_distance_f32': [_ptr, _ptr, _i64, _i64, _i64, _f32, _i64, _ptr, _ptr, _ptr],
-    'mvp_ball_query_distance_f64': [_ptr, _ptr, _i64, _i64, _i64, _f32, _i64, _ptr, _ptr, _ptr],
-    'mvp_ball_query_grid_f32': [_ptr, _ptr, _i64, _i64, _i64, _f32, _i64, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_knn3_grid_f32': [_ptr, _ptr, _i64, _i64, _i64, _f32, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_group_points_forward_strided_f32': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_backward_strided_f32': [_ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_forward_strided_f32': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_backward_strided_f32': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_forward_strided_f64': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_forward_strided_bf16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_backward_strided_f64': [_ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_backward_strided_bf16': [_ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_forward_strided_f64': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_forward_strided_bf16': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_backward_strided_f64': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_backward_strided_bf16': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_forward_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_forward_f64': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_forward_bf16': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_backward_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_backward_f64': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_points_backward_bf16': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_knn_distance_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_knn_distance_f64': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_knn3_weights_f32': [_ptr, _ptr, _i64, _i64, _i64, _f32, _ptr, _ptr, _ptr, _ptr],
-    'mvp_interpolate_forward_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_forward_f64': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_forward_bf16': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_backward_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_backward_f64': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interpolate_backward_bf16': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_unproject_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_unproject_u16': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_pixel_knn_bruteforce_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_pixel_knn_projective_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_lift_gather_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_lift_gather_backward_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_lift_f32': [_ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr,
-                     _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_lift_aug_f32': [_ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr,
-                         _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_lift_store_f32': [_ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr,
-                           _ptr, _ptr, _ptr, _ptr],
-    'mvp_rotate_rows_f32': [_ptr, _ptr, _i64, _i64, _ptr, _ptr],
-    'mvp_copy_slices_f32': [_ptr, _i64, _ptr],
-    'mvp_group_rows_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_rows_backward_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_group_lin_rows_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_group_lin_rows_bn_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_colstats_f32': [_ptr, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_relation_rows_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interp_rows_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_mlp_forward_bf16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _i64, _ptr],
-    'mvp_adam_step_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64] + [ctypes.c_double] * 6 + [_ptr],
-    'mvp_sgd_step_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64] + [ctypes.c_double] * 4 + [ctypes.c_int, _ptr, _ptr],
-    'mvp_grad_sqnorm_partials_f32': [_ptr, _ptr, _i64, _ptr, _ptr, _ptr],
-    'mvp_grad_clip_finish_f32': [_ptr, _ptr, _i64, _ptr, _i64, ctypes.c_double, _ptr, _ptr, _ptr],
-    'mvp_csr_build_i64': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
-    'mvp_csr_build_sorted_i64': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
-    'mvp_gather_rows_backward_csr_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_gather_rows_backward_csr_finish_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_interp_add_rows_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
-    'mvp_interp_add_rows_bn_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_interp_rows_backward_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr],
-    'mvp_bn_rows_forward_f32': [_ptr, _ptr, _ptr, _i64, _i64, _i64, ctypes.c_int, _f32, _f32, ctypes.c_int, _ptr, _ptr, _ptr, _ptr,
-                                _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_bn_rows_backward_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _ptr,
-                                 _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_bn_rows_forward_dropout_f32': [_ptr, _ptr, _ptr, _i64, _i64, ctypes.c_int, _f32, _f32, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
-                                        _ptr, _f32, ctypes.c_uint64, _ptr],
-    'mvp_bn_rows_backward_dropout_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, ctypes.c_int, ctypes.c_int, _ptr, _ptr, _ptr, _ptr,
-                                         _ptr, _f32, ctypes.c_uint64, _ptr],
-    'mvp_bn_rows_backward_finish_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_bn_finalize_f32': [_ptr, _i64, _i64, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_mlp_weight_grad_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_mlp_weight_grad_ws_f32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr],
-    'mvp_mlp_input_grad_f32': [_ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_mlp_input_grad_dropout_f32': [_ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, ctypes.c_uint64, _ptr, _ptr, _ptr, _ptr],
-    'mvp_mlp_layer_backward_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
-                                   _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_mlp_layer_backward_ws_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
-                                   _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_mlp_forward_pool_f32': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _f32,
-                                 _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_pool_finalize_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, ctypes.c_int, _ptr, _ptr, _ptr, _ptr],
-    'mvp_pool_backward_stats_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, ctypes.c_int, _ptr, _ptr, _ptr],
-    'mvp_sa_fused_forward_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr,
-                                 _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_sa_train_forward_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
-                                 _ptr, _ptr, _ptr, _i64, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_sa_train_backward_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
-                                  _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
-                                  _ptr, _ptr],
-    'mvp_sa_train_forward_y2_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
-                                    _ptr, _ptr, _ptr, _i64, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_sa_train_backward_y2_f32': [ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
-                                     _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr,
-                                     _ptr, _ptr, _ptr],
-    'mvp_sa_train_backward1_f32': [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr,
-                                   ctypes.c_int, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_pn2_plan_f32': [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, ctypes.c_int, _f32, _ptr, _i64, _ptr, _ptr, _ptr],
-    'mvp_sa_geom_sums_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_sa_train_stats1_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_sa_train_stats1_ws_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_mlp_forward_bn_f32': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _ptr, _ptr,
-                               _ptr, _ptr, _ptr],
-    'mvp_mlp_forward_rel_bn_f32': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_relation4_rows_f32': [_ptr, _ptr, _i64, _i64, _ptr, _ptr],
-    'mvp_mlp_forward_f32': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    'mvp_vote_accumulate_f32': [_ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_vote_gather_f32': [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_vote_finish_f32': [_ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_lift_vote_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr],
-    'mvp_vote_nearest_f32': [_ptr, _i64, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_seg_loss_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr],
-    'mvp_seg_loss_backward_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
-    'mvp_seg_confusion_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr],
-    'mvp_seg_loss_meter_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr],
-    'mvp_frame_overlap_f32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _ptr, _ptr],
-    'mvp_frame_overlap_u16': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _f32, _ptr, _ptr],
-    'mvp_select_frames_u32': [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_select_frames_ranges_u32': [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_sample_chunks_f32': [_ptr] * 6 + [_i64] * 6 + [ctypes.c_double] * 5 + [ctypes.c_int, ctypes.c_uint64] + [_ptr] * 9 + [_i64, _ptr],
-    'mvp_sample_scenes_f32': [_ptr, _ptr] + [_i64] * 4 + [ctypes.c_uint64] + [_ptr] * 4 + [_i64, _ptr],
-    'mvp_gather_cloud_f32': [_ptr] * 7 + [_i64] * 4 + [_ptr] * 4,
-    'mvp_scene_chunks_count_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _ptr],
-    'mvp_scene_chunks_fill_f32': [_ptr, _i64, _ptr, _i64] + [ctypes.c_double] * 4 + [_ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr],
-    'mvp_pack_chunks_f32': [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _ptr, _i64, _ptr],
-    'mvp_pack_cloud_f32': [_ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _ptr, _ptr, _i64, _ptr],
-    'mvp_ensemble_softmax_f32': [_ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_label_confusion_i64': [_ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr],
-    'mvp_prepare_frames_u8': [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_int, _ptr, _ptr, _ptr],
-    'mvp_resize_bilinear_table': [_i64, _i64, _ptr, _ptr, _ptr, _ptr],  # (host only: no stream)
-    'mvp_resize_nearest_table': [_i64, _i64, _ptr],  # (host only: no stream)
-    'mvp_resize_frames_u8': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr],
-    'mvp_prepare_labels_u16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
-    'mvp_frame_confusion_f32': [_ptr] + [_i64] * 8 + [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr],
-    'mvp_label_histogram_u16': [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
-    'mvp_label_histogram_i64': [_ptr, _i64, _i64, _ptr, _ptr],
-}
-# the shared-MLP entry points with the precision as arguments (csrc/mlp_prec.hip): base parameters + (precision, precision_backward)
-for _n in ['mvp_mlp_forward_f32', 'mvp_mlp_forward_bn_f32', 'mvp_mlp_forward_rel_bn_f32', 'mvp_mlp_forward_pool_f32', 'mvp_mlp_input_grad_f32', 'mvp_mlp_input_grad_dropout_f32',
-           'mvp_mlp_weight_grad_f32', 'mvp_mlp_weight_grad_ws_f32', 'mvp_mlp_layer_backward_f32', 'mvp_mlp_layer_backward_ws_f32',
-           'mvp_sa_fused_forward_f32', 'mvp_sa_train_forward_f32', 'mvp_sa_train_backward_f32', 'mvp_sa_train_forward_y2_f32',
-           'mvp_sa_train_backward_y2_f32']:
-    _SIGNATURES[_n[:-4] + '_p_f32'] = _SIGNATURES[_n][:-1] + [ctypes.c_int, ctypes.c_int, _ptr]
-# (precision as arguments from the start: there is no process-default twin of this one)
-_SIGNATURES['mvp_mlp_layer_backward_wide_p_f32'] = [_ptr] * 9 + [ctypes.c_int, ctypes.c_int, _f32, ctypes.c_uint64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
-                                                    _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, ctypes.c_int, ctypes.c_int, _ptr]
-_SIGNATURES['mvp_mlp_layer_backward_wide_pooled_p_f32'] = [_ptr] * 9 + [ctypes.c_int, ctypes.c_int, _i64, _f32, ctypes.c_uint64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
-                                                           _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, ctypes.c_int, ctypes.c_int, _ptr]
-_SIGNATURES['mvp_mlp_weight_grad_finish_p_f32'] = [_ptr] * 6 + [ctypes.c_int, _ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, ctypes.c_int, ctypes.c_int, _ptr]
-_SIGNATURES['mvp_mlp_weight_grad_finish_rel_p_f32'] = [_ptr] * 6 + [ctypes.c_int, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, ctypes.c_int, ctypes.c_int, _ptr]
-_SIGNATURES['mvp_mlp_weight_grad_finish_act_p_f32'] = [_ptr] * 6 + [ctypes.c_int, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, ctypes.c_int,
-                                                        ctypes.c_int, _ptr]
-_SIGNATURES['mvp_mlp_input_grad_wide_p_f32'] = [_ptr] * 8 + [ctypes.c_int, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64,
-                                                 ctypes.c_int, ctypes.c_int, _ptr]
-EXPORTS = ['mvp_version', 'mvp_strerror', 'mvp_lift_workspace_bytes', 'mvp_ball_query_grid_workspace', 'mvp_knn3_grid_workspace', 'mvp_vote_nearest_workspace', 'mvp_sample_chunks_workspace', 'mvp_sample_scenes_workspace', 'mvp_prepare_frames_workspace', 'mvp_mlp_weight_grad_workspace_floats', 'mvp_mlp_input_grad_wide_workspace_bytes', 'mvp_group_lin_partial_count', 'mvp_colstats_partial_count', 'mvp_grad_clip_partials_count',
-           'mvp_set_mlp_precision', 'mvp_get_mlp_precision', 'mvp_mlp_layer_backward_partial_count', 'mvp_set_mlp_stream', 'mvp_set_mlp_precision_backward', 'mvp_get_mlp_precision_backward', 'mvp_mlp_precision_scope', 'mvp_set_fps_mode', 'mvp_fps_debug_spin_limit', 'mvp_fps_last_kernel'] + sorted(_SIGNATURES)
+# The closed type map of the C ABI.  Any pointer is a c_void_p; a return may also be size_t or const char*.  Anything else raises.
+_C_TYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double,
+            'mvp_stream_t': ctypes.c_void_p}
+_C_RETURN_TYPES = {'size_t': ctypes.c_size_t, 'const char*': ctypes.c_char_p}
+
+
+def _ctype(decl, proto, returns=False):
+    decl = ' '.join(decl.split()).replace(' *', '*')
+    if returns and decl in _C_RETURN_TYPES:
+        return _C_RETURN_TYPES[decl]
+    if decl.endswith('*'):
+        return ctypes.c_void_p
+    if decl not in _C_TYPES:
+        raise RuntimeError('include/mvp_hip.h: no ctypes type for {!r} in the prototype `{}`'.format(decl, proto))
+    return _C_TYPES[decl]
+
+
+def _parse_header(text):
+    """-> (name -> argtypes, name -> restype, MVP_* macro -> int) of the header `text`: every statement outside comments and preprocessor
+    lines is a prototype of an mvp_* function (or the typedef of mvp_stream_t); one this cannot read raises, nothing is guessed."""
+    text = re.sub(r'//[^\n]*', ' ', re.sub(r'/\*.*?\*/', ' ', text, flags=re.S))
+    limits = {m.group(1): int(m.group(2) or m.group(3))
+              for m in re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(MVP_\w+)[ \t]+(?:(-?\d+)|\([ \t]*(-?\d+)[ \t]*\))[ \t]*$', text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+    text = re.sub(r'\bextern\s+"C"\s*\{(.*)\}', r'\1', text, flags=re.S)
+    signatures, restypes = {}, {}
+    for statement in text.split(';'):
+        proto = ' '.join(statement.split())
+        if not proto or proto == 'typedef void* mvp_stream_t':
+            continue
+        m = re.fullmatch(r'(.+?)\b(mvp_\w+) ?\((.*)\)', proto)
+        if not m or m.group(2) in signatures:
+            raise RuntimeError('include/mvp_hip.h: not a prototype the loader can read, or a second one of that name: `{}`'.format(proto))
+        argtypes = []
+        for param in ([] if m.group(3).strip() in ('', 'void') else m.group(3).split(',')):
+            p = re.fullmatch(r'(.*[\w*]) ?\b(\w+)', param.strip())
+            if not p or p.group(2) == 'const':
+                raise RuntimeError('include/mvp_hip.h: cannot split the parameter {!r} of `{}` into type and name'.format(param.strip(), proto))
+            argtypes.append(_ctype(p.group(1), proto))
+        signatures[m.group(2)] = argtypes
+        restypes[m.group(2)] = _ctype(m.group(1), proto, returns=True)
+    return signatures, restypes, limits
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError('include/mvp_hip.h is missing ({}): the ctypes signatures of libmvp_hip.so are read from it'.format(HEADER_PATH))
+with open(HEADER_PATH) as _f:
+    _header = _f.read()
+# name -> argtypes and name -> restype of every entry point; LIMITS: the header's integer #defines (MVP_*_MAX_* and the status codes)
+_SIGNATURES, _RESTYPES, LIMITS = _parse_header(_header)
+EXPORTS = sorted(_SIGNATURES)
 
 
 def lib():
@@ -196,68 +77,19 @@ def lib():
             raise RuntimeError('libmvp_hip.so is not built: run `python -c "import __graft_entry__ as g; g.build()"` '
                                'or `make -C mvpnet_amd/csrc` ({})'.format(LIB_PATH))
         handle = ctypes.CDLL(LIB_PATH)
-        handle.mvp_version.restype = ctypes.c_char_p
-        handle.mvp_strerror.restype = ctypes.c_char_p
-        handle.mvp_strerror.argtypes = [ctypes.c_int]
-        handle.mvp_lift_workspace_bytes.restype = ctypes.c_int64
-        handle.mvp_lift_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _i64]
-        handle.mvp_ball_query_grid_workspace.restype = ctypes.c_int64
-        handle.mvp_ball_query_grid_workspace.argtypes = [_i64, _i64, _i64]
-        handle.mvp_knn3_grid_workspace.restype = ctypes.c_int64
-        handle.mvp_knn3_grid_workspace.argtypes = [_i64, _i64, _i64]
-        handle.mvp_vote_nearest_workspace.restype = ctypes.c_int64
-        handle.mvp_vote_nearest_workspace.argtypes = [_i64, _i64]
-        handle.mvp_sample_chunks_workspace.restype = ctypes.c_int64
-        handle.mvp_sample_chunks_workspace.argtypes = [_i64, _i64, _i64, _i64]
-        handle.mvp_sample_scenes_workspace.restype = ctypes.c_int64
-        handle.mvp_sample_scenes_workspace.argtypes = [_i64, _i64, _i64]
-        handle.mvp_prepare_frames_workspace.restype = ctypes.c_size_t
-        handle.mvp_prepare_frames_workspace.argtypes = [_i64]
-        handle.mvp_group_lin_partial_count.restype = ctypes.c_int64
-        handle.mvp_group_lin_partial_count.argtypes = [_i64, _i64, _i64, _i64]
-        handle.mvp_mlp_weight_grad_workspace_floats.restype = ctypes.c_int64
-        handle.mvp_mlp_weight_grad_workspace_floats.argtypes = []
-        handle.mvp_mlp_input_grad_wide_workspace_bytes.restype = ctypes.c_int64
-        handle.mvp_mlp_input_grad_wide_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
-        handle.mvp_colstats_partial_count.restype = ctypes.c_int64
-        handle.mvp_colstats_partial_count.argtypes = [_i64, _i64]
-        handle.mvp_grad_clip_partials_count.restype = ctypes.c_int64
-        handle.mvp_grad_clip_partials_count.argtypes = [_ptr, _i64]
-        handle.mvp_set_mlp_precision.restype = ctypes.c_int
-        handle.mvp_set_mlp_precision.argtypes = [ctypes.c_int, ctypes.c_int]
-        handle.mvp_get_mlp_precision.restype = ctypes.c_int
-        handle.mvp_get_mlp_precision.argtypes = []
-        handle.mvp_mlp_layer_backward_partial_count.restype = ctypes.c_int64
-        handle.mvp_mlp_layer_backward_partial_count.argtypes = [_i64, _i64]
         for name, argtypes in _SIGNATURES.items():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
+            fn.restype = _RESTYPES[name]
         _lib = handle
-        handle.mvp_set_mlp_stream.restype = ctypes.c_int
-        handle.mvp_set_mlp_stream.argtypes = [ctypes.c_int]
-        handle.mvp_set_fps_mode.restype = ctypes.c_int
-        handle.mvp_set_fps_mode.argtypes = [ctypes.c_int]
-        handle.mvp_fps_debug_spin_limit.restype = ctypes.c_int
-        handle.mvp_fps_debug_spin_limit.argtypes = [ctypes.c_int]
-        handle.mvp_fps_last_kernel.restype = ctypes.c_int
-        handle.mvp_fps_last_kernel.argtypes = []
         if os.environ.get('MVP_MLP_STREAM') is not None:
             handle.mvp_set_mlp_stream(int(os.environ['MVP_MLP_STREAM']))
-        handle.mvp_set_mlp_precision_backward.restype = ctypes.c_int
-        handle.mvp_set_mlp_precision_backward.argtypes = [ctypes.c_int]
-        handle.mvp_get_mlp_precision_backward.restype = ctypes.c_int
-        handle.mvp_get_mlp_precision_backward.argtypes = []
-        handle.mvp_mlp_precision_scope.restype = ctypes.c_int
-        handle.mvp_mlp_precision_scope.argtypes = [ctypes.c_int, ctypes.c_int]
         if os.environ.get('MVP_MLP_PRECISION_BWD'):
             check(handle.mvp_set_mlp_precision_backward(MLP_PRECISIONS[os.environ['MVP_MLP_PRECISION_BWD']]), 'mvp_set_mlp_precision_backward')
         env = os.environ.get('MVP_MLP_PRECISION')
         if env:
             set_mlp_precision(env, int(os.environ.get('MVP_MLP_MIN_WIDTH', '0')))
     return _lib
-
-
 
 
 def set_mlp_precision(name, min_width=0):
@@ -268,17 +100,15 @@ def set_mlp_precision(name, min_width=0):
     if name not in MLP_PRECISIONS:
         raise ValueError('mlp precision must be one of {}'.format(sorted(MLP_PRECISIONS)))
     check(lib().mvp_set_mlp_precision(MLP_PRECISIONS[name], int(min_width)), 'mvp_set_mlp_precision')
-    global _mlp_min_width
-    _mlp_min_width = int(min_width)
-
-
-_mlp_min_width = 0
 
 
 def mlp_min_width():
-    """The `min_width` of the last set_mlp_precision (layers narrower than it stay on the fp32 MFMA): the hosts of the split-bf16-only entry
-    points (rows.wide_backward_ok, the finish-on-load weight gradient) leave such layers to the per-layer kernels."""
-    return _mlp_min_width
+    """The `min_width` the library holds (mvp_get_mlp_min_width; layers narrower than it stay on the fp32 MFMA): the hosts of the
+    split-bf16-only entry points (rows.wide_backward_ok, the finish-on-load weight gradient) leave such layers to the per-layer kernels."""
+    return (_lib if _lib is not None else _load()).mvp_get_mlp_min_width()
+
+
+_load = lib  # mlp_min_width asks the loaded library itself: a state query, not a launch, so it does not go through a stand-in for `lib` / `_fn`
 
 
 def set_mlp_precision_backward(name):

@@ -1454,6 +1454,7 @@ MVP_API int mvp_set_mlp_precision(int terms, int min_width) {
   return MVP_OK;
 }
 MVP_API int mvp_get_mlp_precision(void) { return mlp_terms(); }
+MVP_API int mvp_get_mlp_min_width(void) { return g_mlp_min_width; }
 // Split of the GRADIENT contractions (weight gradient, input gradient, one-kernel layer backward) when the forward precision is a
 // split one: terms = 3 (default) or 6.  Gradients through batch-statistics BatchNorm + max pooling carry ~1 % fp32 noise whatever the
 // contraction (profiles/r02_numerics_operating_point.txt); 2^-17 per product is invisible next to it and halves their MFMA + split work.

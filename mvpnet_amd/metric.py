@@ -263,7 +263,7 @@ class DeviceEvaluator(object):
     overall_iou = Evaluator.overall_iou
 
 
-MAX_WINDOW = 64  # MVP_SEG_METER_MAX_WINDOW
+MAX_WINDOW = L.LIMITS['MVP_SEG_METER_MAX_WINDOW']
 
 
 def meter_state_sizes(num_classes, window):

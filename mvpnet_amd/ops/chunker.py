@@ -4,10 +4,10 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from .overlap import MAX_BASE_POINTS  # MVP_OVERLAP_MAX_BASE
+from .overlap import MAX_BASE_POINTS
 
-MAX_WINDOWS = 65535  # MVP_CHUNKER_MAX_WINDOWS
-MAX_CLOUD_CHANNELS = 8  # MVP_PACK_CLOUD_MAX_CHANNELS
+MAX_WINDOWS = L.LIMITS['MVP_CHUNKER_MAX_WINDOWS']
+MAX_CLOUD_CHANNELS = L.LIMITS['MVP_PACK_CLOUD_MAX_CHANNELS']
 
 
 def supported(n, nc, nb=0):

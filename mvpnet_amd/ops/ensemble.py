@@ -6,9 +6,9 @@ import torch
 
 from .. import _lib as L
 
-MAX_MODELS = 8  # MVP_ENSEMBLE_MAX_MODELS
+MAX_MODELS = L.LIMITS['MVP_ENSEMBLE_MAX_MODELS']
 MAX_CLASSES = 64
-MAX_CONFUSION_CLASSES = 32768  # MVP_CONFUSION_MAX_CLASSES
+MAX_CONFUSION_CLASSES = L.LIMITS['MVP_CONFUSION_MAX_CLASSES']
 
 
 def ensemble_softmax(logits, want_prob=True):

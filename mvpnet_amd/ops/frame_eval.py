@@ -6,7 +6,7 @@ import torch
 from .. import _lib as L
 from .resize import _nearest_on, _size
 
-MAX_BINS = 65536  # MVP_HISTOGRAM_MAX_BINS
+MAX_BINS = L.LIMITS['MVP_HISTOGRAM_MAX_BINS']
 
 _ALL = {}  # (device, Ftot) -> arange(Ftot) int64 on the device, for picked=None
 

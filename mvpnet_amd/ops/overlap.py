@@ -7,7 +7,7 @@ import torch
 
 from .. import _lib as L
 
-MAX_BASE_POINTS = 4096   # MVP_OVERLAP_MAX_BASE: the base points of mvp_frame_overlap_* live in LDS
+MAX_BASE_POINTS = L.LIMITS['MVP_OVERLAP_MAX_BASE']  # the base points of mvp_frame_overlap_* live in LDS
 MAX_SELECT_WORDS = 1024  # mvp_select_frames_u32 keeps the uncovered set in LDS
 
 

@@ -4,9 +4,9 @@ import torch
 
 from .. import _lib as L
 
-MAX_NB_PTS = 8192   # MVP_SAMPLE_MAX_PTS: the crop sorts its (key, index) pairs in LDS
-MAX_TRIES = 32      # MVP_SAMPLE_MAX_TRIES
-MAX_CHUNKS = 65535  # MVP_SAMPLE_MAX_CHUNKS
+MAX_NB_PTS = L.LIMITS['MVP_SAMPLE_MAX_PTS']  # the crop sorts its (key, index) pairs in LDS
+MAX_TRIES = L.LIMITS['MVP_SAMPLE_MAX_TRIES']
+MAX_CHUNKS = L.LIMITS['MVP_SAMPLE_MAX_CHUNKS']
 
 _WORKSPACE = {}
 

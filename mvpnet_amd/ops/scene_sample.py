@@ -6,7 +6,7 @@ import torch
 from .. import _lib as L
 from .sample import MAX_CHUNKS, _i64, _seed, _workspace
 
-MAX_SCENE_NB_PTS = 65536  # MVP_SAMPLE_SCENE_MAX_PTS: what the sampler's multi-workgroup FPS serves
+MAX_SCENE_NB_PTS = L.LIMITS['MVP_SAMPLE_SCENE_MAX_PTS']  # what the sampler's multi-workgroup FPS serves
 
 
 def _scenes(scene_offsets, scene_of_row, who):

@@ -36,7 +36,7 @@ def test_signature_table_matches_the_header_argument_counts():
     for name, sig in _lib._SIGNATURES.items():
         m = re.search(r'\b' + name + r'\s*\(([^;]*?)\)\s*;', text, flags=re.S)
         assert m, name
-        n = len([a for a in m.group(1).split(',') if a.strip()])
+        n = len([a for a in m.group(1).split(',') if a.strip() not in ('', 'void')])   # `(void)`: no parameters
         assert n == len(sig), (name, n, len(sig))
 
 
@@ -65,7 +65,7 @@ def test_set_abstraction_level_limits_are_refused_before_any_launch():
     C1, C2, C3 = 64, 64, 128
     # a split-bf16 precision, set here: without one the entry points answer MVP_EUNSUPPORTED before they look at the limits
     old = lib.mvp_get_mlp_precision(), lib.mvp_get_mlp_precision_backward()
-    assert lib.mvp_set_mlp_precision(6, _lib._mlp_min_width) == 0 and lib.mvp_set_mlp_precision_backward(3) == 0
+    assert lib.mvp_set_mlp_precision(6, _lib.mlp_min_width()) == 0 and lib.mvp_set_mlp_precision_backward(3) == 0
 
     def level(B, N, M, K, xyz):   # zf, xyz, centre, index, wxyz, B, N, M, K, C1, bn1 x 4, W2, C2, bn2 x 4, W3, C3
         return (d, xyz, d, d, d, B, N, M, K, C1, d, d, d, d, d, C2, d, d, d, d, d, C3)
@@ -90,7 +90,7 @@ def test_set_abstraction_level_limits_are_refused_before_any_launch():
             assert entry(2 ** 20, 1000, 2 ** 11, 32, None) == -3 and entry(2, 2 ** 31, 10, 0, d) == -1
             assert entry(2, 1000, 10, 0, None) == -3             # a null pointer outranks an invalid size
     finally:
-        assert lib.mvp_set_mlp_precision(old[0], _lib._mlp_min_width) == 0 and lib.mvp_set_mlp_precision_backward(old[1]) == 0
+        assert lib.mvp_set_mlp_precision(old[0], _lib.mlp_min_width()) == 0 and lib.mvp_set_mlp_precision_backward(old[1]) == 0
 
 
 @pytest.mark.parametrize('fn', ['fps', 'ball', 'knn', 'group', 'interp'])
@@ -142,3 +142,100 @@ def test_thread_local_precision_scope():
     with L.mlp_precision('bf16', backward='bf16'):  # plain bf16 operands, one product (opt-in)
         assert lib.mvp_get_mlp_precision() == 1 and lib.mvp_get_mlp_precision_backward() == 1
     assert lib.mvp_get_mlp_precision() == default
+
+
+def test_derived_types_of_pinned_prototypes():
+    """The tables mvpnet_amd/_lib.py derives from the header against hand-written argtypes AND restype of prototypes that between them use
+    every C type of the header: a c_int for an int64_t, a c_float for a double or a status restype on a size_t return shows here."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+    from mvpnet_amd import _lib as L
+    p, i64 = c_void_p, c_int64
+    pinned = {
+        'mvp_adam_step_f32': ([p] * 5 + [i64] + [c_double] * 6 + [p], c_int),
+        'mvp_sample_chunks_f32': ([p] * 6 + [i64] * 6 + [c_double] * 5 + [c_int, c_uint64] + [p] * 9 + [i64, p], c_int),
+        'mvp_bn_rows_forward_dropout_f32': ([p, p, p, i64, i64, c_int, c_float, c_float, c_int] + [p] * 7 + [c_float, c_uint64, p], c_int),
+        'mvp_lift_f32': ([p, c_int] + [p] * 6 + [i64] * 7 + [p] * 7, c_int),
+        'mvp_pn2_plan_f32': ([p, i64, i64, i64, p, p, p, p, c_int, c_int, c_float, p, i64, p, p, p], c_int),
+        'mvp_prepare_frames_workspace': ([i64], c_size_t),
+        'mvp_lift_workspace_bytes': ([i64] * 5, c_int64),
+        'mvp_version': ([], c_char_p),
+        'mvp_strerror': ([c_int], c_char_p),
+    }
+    for name, (argtypes, restype) in pinned.items():
+        assert L._SIGNATURES[name] == argtypes, name
+        assert L._RESTYPES[name] is restype, name
+    assert set(L._RESTYPES) == set(L._SIGNATURES) and L.EXPORTS == sorted(L._SIGNATURES)
+
+
+def test_derived_types_are_applied_to_every_function():
+    """lib() sets argtypes and restype of EVERY entry point, the ones that return no status or take no stream included."""
+    from mvpnet_amd import _lib as L
+    lib = L.lib()
+    assert len(L._SIGNATURES) == len(declared_symbols())
+    for name in L._SIGNATURES:
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == L._SIGNATURES[name], name
+        assert fn.restype is L._RESTYPES[name], name
+
+
+def test_header_parser_is_strict():
+    import ctypes
+    from mvpnet_amd import _lib as L
+    with pytest.raises(RuntimeError, match='mvp_bad_f32'):      # a scalar type outside the closed map names its prototype
+        L._parse_header('int mvp_ok(int a);\nint mvp_bad_f32(const float* x, unsigned n, mvp_stream_t stream);')
+    with pytest.raises(RuntimeError, match='mvp_bad_f32'):
+        L._parse_header('uint8_t mvp_bad_f32(void);')
+    with pytest.raises(RuntimeError, match='mvp_unnamed'):      # a parameter that does not split into type and name
+        L._parse_header('int mvp_unnamed(int64_t, float* out);')
+    with pytest.raises(RuntimeError, match='mvp_unnamed'):
+        L._parse_header('int mvp_unnamed(int64_t n, float* const);')
+    with pytest.raises(RuntimeError, match='struct'):           # a statement that is no prototype
+        L._parse_header('struct mvp_s { int a; };')
+    with pytest.raises(RuntimeError, match='mvp_twice'):
+        L._parse_header('int mvp_twice(int a);\nint mvp_twice(int64_t a);')
+    sig, res, limits = L._parse_header(
+        '/* int mvp_x(int a); */\n'
+        '// int mvp_y(int a);\n'
+        '#define MVP_A_MAX_B 12   /* a limit */\n'
+        '#define MVP_ENEG (-7)\n'
+        '#define MVP_WORDS(C) (4 + (C))\n'
+        '#define MVP_RATIO 0.5\n'
+        '#define MVP_GUARD_H_\n'
+        'typedef void* mvp_stream_t;\n'
+        'int64_t mvp_three_lines_f32(const float* x,   /* mvp_z(1); */\n'
+        '                            double scale, uint64_t seed,\n'
+        '                            float *const *outs, mvp_stream_t stream);\n'
+        'size_t mvp_nothing(void);\n')
+    assert sig == {'mvp_three_lines_f32': [ctypes.c_void_p, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p], 'mvp_nothing': []}
+    assert res == {'mvp_three_lines_f32': ctypes.c_int64, 'mvp_nothing': ctypes.c_size_t}
+    assert limits == {'MVP_A_MAX_B': 12, 'MVP_ENEG': -7}
+
+
+def test_limits_come_from_the_header():
+    from mvpnet_amd import _lib as L
+    from mvpnet_amd import metric
+    from mvpnet_amd.ops import chunker, ensemble, frame_eval, overlap, sample, scene_sample
+    expected = {'MVP_OVERLAP_MAX_BASE': 4096, 'MVP_SAMPLE_MAX_PTS': 8192, 'MVP_SAMPLE_MAX_TRIES': 32, 'MVP_SAMPLE_MAX_CHUNKS': 65535,
+                'MVP_SAMPLE_SCENE_MAX_PTS': 65536, 'MVP_CHUNKER_MAX_WINDOWS': 65535, 'MVP_PACK_CLOUD_MAX_CHANNELS': 8,
+                'MVP_SEG_METER_MAX_WINDOW': 64, 'MVP_ENSEMBLE_MAX_MODELS': 8, 'MVP_CONFUSION_MAX_CLASSES': 32768, 'MVP_HISTOGRAM_MAX_BINS': 65536}
+    assert {k: v for k, v in L.LIMITS.items() if '_MAX_' in k} == expected
+    assert (L.LIMITS['MVP_OK'], L.LIMITS['MVP_EINVAL'], L.LIMITS['MVP_EUNSUPPORTED'], L.LIMITS['MVP_ENULL']) == (0, -1, -2, -3)
+    constants = {'MVP_OVERLAP_MAX_BASE': overlap.MAX_BASE_POINTS, 'MVP_SAMPLE_MAX_PTS': sample.MAX_NB_PTS, 'MVP_SAMPLE_MAX_TRIES': sample.MAX_TRIES,
+                 'MVP_SAMPLE_MAX_CHUNKS': sample.MAX_CHUNKS, 'MVP_SAMPLE_SCENE_MAX_PTS': scene_sample.MAX_SCENE_NB_PTS,
+                 'MVP_CHUNKER_MAX_WINDOWS': chunker.MAX_WINDOWS, 'MVP_PACK_CLOUD_MAX_CHANNELS': chunker.MAX_CLOUD_CHANNELS,
+                 'MVP_SEG_METER_MAX_WINDOW': metric.MAX_WINDOW, 'MVP_ENSEMBLE_MAX_MODELS': ensemble.MAX_MODELS,
+                 'MVP_CONFUSION_MAX_CLASSES': ensemble.MAX_CONFUSION_CLASSES, 'MVP_HISTOGRAM_MAX_BINS': frame_eval.MAX_BINS}
+    assert constants == expected and chunker.MAX_BASE_POINTS == expected['MVP_OVERLAP_MAX_BASE']
+
+
+def test_min_width_is_read_from_the_library():
+    """mvp_set_mlp_precision called directly, past the Python setter: mlp_min_width() follows (it routes layers between kernels)."""
+    from mvpnet_amd import _lib as L
+    lib = L.lib()
+    terms, width = lib.mvp_get_mlp_precision(), L.mlp_min_width()
+    try:
+        assert lib.mvp_set_mlp_precision(terms, 48) == 0
+        assert L.mlp_min_width() == 48
+    finally:
+        assert lib.mvp_set_mlp_precision(terms, width) == 0
+    assert L.mlp_min_width() == width
