@@ -721,6 +721,38 @@ int mvp_mlp_precision_scope(int terms, int terms_backward);
  * step >= 1 is the number of THIS update; fp32 arithmetic, the bias corrections in double on the host.  96 tensors per launch. */
 int mvp_adam_step_f32(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
                       int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, double step, mvp_stream_t stream);
+/* The same step with its step number and learning rate ON THE DEVICE (adam.hip), so that a captured graph which holds these launches
+ * takes update t + 1 at the current learning rate on every replay.  None of the three synchronises or allocates; every check below
+ * happens before any launch.
+ *   mvp_adam_advance_f32: one small launch.  step_counts: n_counts float32 values on the device, the `step` of every parameter of a
+ *       group, all equal (the caller's rule); lr: one double on the device; hyper: MVP_SOLVER_HYPER_F32 floats on the device.  Adds 1.0f
+ *       to every count, takes t = (int64)step_counts[0] after the add (a float32 count is exact below 2^24 updates) and writes, all in
+ *       double, every operation rounded once, nothing contracted, no pow():
+ *           pow_int(b, t):  r = 1; x = b; while (t) { if (t & 1) r = r * x; x = x * x; t >>= 1; }
+ *           bc1 = 1 - pow_int(beta1, t);  bc2 = 1 - pow_int(beta2, t)
+ *           hyper[0] = (float)(lr / bc1);  hyper[1] = (float)sqrt(bc2) (a correctly rounded double sqrt);  hyper[2] = (float)lr;  hyper[3] = 0
+ *       -- a function of the count alone, the same bits wherever it is restated (host and device pow() may differ in the last place, so
+ *       mvp_adam_step_f32's corrections may differ from these by one place of the two float32 factors).
+ *       MVP_ENULL (step_counts, lr, hyper); MVP_EINVAL unless n_counts >= 1 and both betas in [0, 1).
+ *   mvp_adam_step_dev_f32: mvp_adam_step_f32's update and launches (96 tensors each, same vector / tail / unaligned paths) with
+ *       step_size = hyper[0] and bc2_sqrt = hyper[1] read on the device; 1 - beta in double on the host as there.  grad_scale: NULL or a
+ *       DEVICE pointer to one float: g' = g * grad_scale, one rounded product as the gradient is read, before the weight decay -- the
+ *       arithmetic of mvp_sgd_step_f32's grad_scale and of mvp_grad_clip_finish_f32's in-place scale; the gradients are not written.
+ *       mvp_adam_step_f32's argument checks (no step); hyper NULL with n > 0: MVP_ENULL.
+ *   mvp_lr_multistep_f64: torch's MultiStepLR in its chainable form (group['lr'] * gamma ** milestones[last_epoch]) in the same doubles,
+ *       one small launch:  e = *epoch + 1;  for i < n_milestones: if (milestones[i] == e) for g < n_groups: lr[g] = lr[g] * factors[i];
+ *       *epoch = e.  epoch: one int64 and lr: n_groups doubles on the device; milestones (distinct, strictly ascending) and factors
+ *       (gamma ** multiplicity, evaluated by the caller) are HOST arrays that travel by value in the argument block.
+ *       MVP_ENULL (epoch, lr; milestones, factors when n_milestones > 0); MVP_EINVAL unless n_groups >= 1, n_milestones >= 0, the
+ *       milestones strictly ascending and no factor NaN; MVP_EUNSUPPORTED for n_milestones > MVP_SOLVER_MILESTONE_SLOTS. */
+#define MVP_SOLVER_MILESTONE_SLOTS 16
+#define MVP_SOLVER_HYPER_F32 4      /* step_size, bc2_sqrt, (float)lr, reserved */
+int mvp_adam_advance_f32(float* step_counts, int64_t n_counts, const double* lr, double beta1, double beta2, float* hyper, mvp_stream_t stream);
+int mvp_adam_step_dev_f32(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
+                          int64_t n, const float* hyper, const float* grad_scale, double beta1, double beta2, double eps, double weight_decay,
+                          mvp_stream_t stream);
+int mvp_lr_multistep_f64(int64_t* epoch, double* lr, int64_t n_groups, const int64_t* milestones, const double* factors, int64_t n_milestones,
+                         mvp_stream_t stream);
 /* One SGD step of n float32 tensors (solver.hip; replaces, on the GPU, torch.optim.SGD.step of the reference's 2D stage:
  * common/solver/build.py:7-22 with configs/scannet/unet_resnet34.yaml).  params / grads / momentum_buf: HOST arrays of n device pointers,
  * numel their element counts (< 2^31 each), first: a HOST array of n bytes, grad_scale: NULL or a DEVICE pointer to one float (a clip

@@ -308,14 +308,20 @@ def build_batch_3d(cfg, training=True):
     return kwargs
 
 
-def build_optimizer(cfg, model):
-    """common/solver/build.py:7-22"""
+def build_optimizer(cfg, model, capturable=False):
+    """common/solver/build.py:7-22.  capturable=True (opt-in): the FusedAdam whose step number and learning rate live on the device, for a
+    captured training step (mvpnet3d.GraphedTrainStep(solver='captured')); a ValueError for anything but Adam on float32 GPU parameters."""
     import torch
     name = cfg.OPTIMIZER.TYPE
-    if name == '':
+    if name == '' and not capturable:
         return None
-    kwargs = dict(cfg.OPTIMIZER.get(name, {}))
+    kwargs = dict(cfg.OPTIMIZER.get(name, {})) if name else {}
     params = [p for p in model.parameters()]
+    if capturable:
+        if name != 'Adam' or kwargs.get('amsgrad') or 'fused' in kwargs or not params or not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+            raise ValueError('build_optimizer(capturable=True) covers OPTIMIZER.TYPE Adam (no amsgrad) on float32 GPU parameters, not {!r}'.format(name))
+        from .optim import FusedAdam
+        return FusedAdam(params, lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY, capturable=True, **kwargs)
     if name == 'Adam' and not kwargs.get('amsgrad') and 'fused' not in kwargs and params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
         from .optim import FusedAdam  # a torch.optim.Adam (same state, same checkpoints) whose step is ONE launch for all parameter tensors
         return FusedAdam(params, lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY, **kwargs)
@@ -328,10 +334,17 @@ def build_optimizer(cfg, model):
     return getattr(torch.optim, name)(params, lr=cfg.OPTIMIZER.BASE_LR, weight_decay=cfg.OPTIMIZER.WEIGHT_DECAY, **kwargs)
 
 
-def build_scheduler(cfg, optimizer):
-    """common/solver/build.py:25-41 (without ClipLR)"""
+def build_scheduler(cfg, optimizer, capturable=False):
+    """common/solver/build.py:25-41 (without ClipLR).  capturable=True (opt-in): optim.DeviceMultiStepLR on a capturable FusedAdam; a
+    ValueError for anything but MultiStepLR on such an optimizer."""
     import torch
     name = cfg.SCHEDULER.TYPE
+    if capturable:
+        from .optim import DeviceMultiStepLR, FusedAdam
+        if name != 'MultiStepLR' or not (isinstance(optimizer, FusedAdam) and optimizer.capturable):
+            raise ValueError('build_scheduler(capturable=True) covers SCHEDULER.TYPE MultiStepLR on a FusedAdam(capturable=True), not {!r} on {}'.format(
+                name, type(optimizer).__name__))
+        return DeviceMultiStepLR(optimizer, **dict(cfg.SCHEDULER.get(name, {})))
     if name == '':
         return None
     return getattr(torch.optim.lr_scheduler, name)(optimizer, **dict(cfg.SCHEDULER.get(name, {})))

@@ -533,7 +533,13 @@ class GraphedTrainStep:
     The graph holds, for fixed shapes: lifting of batch i -> FORK: FPS / ball query / 3-NN of batch i+1 on the side stream ->
     aggregation + PointNet++ of batch i with the geometry computed by the PREVIOUS replay -> loss -> backward -> JOIN -> copy
     of the new geometry into the static plan.  Gradient all-reduce, clipping, optimizer and scheduler stay eager after the
-    replay (they are a handful of multi-tensor launches, and RCCL stays out of the capture).
+    replay (they are a handful of multi-tensor launches, and RCCL stays out of the capture) -- unless solver='captured'.
+
+    solver='captured' (opt-in; needs optim.FusedAdam(capturable=True), scheduler None or an optim.DeviceMultiStepLR, and no grad_sync):
+    the clip coefficient (optim.total_grad_norm, only when max_grad_norm > 0), optimizer.step(grad_scale=coef) and scheduler.step() are
+    nodes of the graph behind the plan copy -- the step number and the learning rate live on the device, so every replay takes the next
+    update --, and step() is the input copies and one replay.  The gradients are left UNSCALED: the coefficient is applied while the
+    step kernel reads them (the deferred scale of FusedSGD.step(grad_scale=)), so `.grad` after a step holds the unclipped gradient.
 
     step(batch, next_batch) copies the two batches into the static input tensors (keys of the reference's data dict; the 2D
     feature map is produced inside the graph by model.net_2d) and replays.  Batches must arrive in sequence: `batch` of call
@@ -546,7 +552,7 @@ class GraphedTrainStep:
     COPY_KEYS = ('images', 'points', 'seg_label', 'depth', 'cam_matrix', 'kinv', 'pose', 'pixel_box', 'image_xyz', 'knn_indices', 'flip', 'z_rot')
 
     def __init__(self, model, loss_fn, optimizer, batch, next_batch, scheduler=None, max_grad_norm=0.0, grad_sync=None, warmup=3,
-                 geometry='captured', plan=None):
+                 geometry='captured', plan=None, solver='eager'):
         """plan: the static geometry plan of ANOTHER GraphedTrainStep of the same model and shapes (PipelinedTrainStep: several captured copies
         of the step replayed in turn hand the next batch's geometry to each other through one set of plan tensors).
         geometry='captured' (default): the fork / join of the next batch's coordinate-only work lives inside the graph (no per-step
@@ -556,6 +562,17 @@ class GraphedTrainStep:
         9.43 ms for the plain eager step on the same box -- the replay itself, not the fork, is what trails the eager stream by 4 %."""
         assert geometry in ('eager', 'captured')
         self.geometry = geometry
+        if solver not in ('eager', 'captured'):
+            raise ValueError("GraphedTrainStep: solver is 'eager' or 'captured', not {!r}".format(solver))
+        if solver == 'captured':
+            from . import optim
+            if not (isinstance(optimizer, optim.FusedAdam) and optimizer.capturable):
+                raise ValueError("GraphedTrainStep(solver='captured') needs an optim.FusedAdam(capturable=True)")
+            if scheduler is not None and not isinstance(scheduler, optim.DeviceMultiStepLR):
+                raise ValueError("GraphedTrainStep(solver='captured') takes no scheduler or an optim.DeviceMultiStepLR (others write host floats)")
+            if grad_sync is not None:
+                raise ValueError("GraphedTrainStep(solver='captured') takes no grad_sync: the all-reduce stays out of the capture")
+        self.solver = solver
         self.model, self.loss_fn, self.optimizer = model, loss_fn, optimizer
         self.scheduler, self.max_grad_norm, self.grad_sync = scheduler, max_grad_norm, grad_sync
         net = model.module if hasattr(model, 'module') else model
@@ -576,6 +593,8 @@ class GraphedTrainStep:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.plan = plan  # static geometry of the CURRENT batch
+        if solver == 'captured':
+            optimizer.materialize()  # moments, counts and device learning rates exist before the capture (the warm-up's gradients say which)
         optimizer.zero_grad(set_to_none=True)
         R.weight_slices.refresh(dev)  # the slice table exists before the capture: the refresh launch becomes a node of the graph
         self.graph = torch.cuda.CUDAGraph()
@@ -607,6 +626,14 @@ class GraphedTrainStep:
                 for dst, src in zip(_plan_tensors(self.plan), _plan_tensors(new_plan)):
                     dst.copy_(src)
             self.preds = preds
+            if self.solver == 'captured':
+                from . import optim
+                coef = None
+                if self.max_grad_norm > 0:
+                    self.grad_norm, coef = optim.total_grad_norm(list(model.parameters()), self.max_grad_norm)
+                self.optimizer.step(grad_scale=coef)
+                if self.scheduler is not None:
+                    self.scheduler.step()
 
     def step(self, batch=None, next_batch=None):
         if batch is not None:
@@ -630,6 +657,8 @@ class GraphedTrainStep:
             del net
         else:
             self.graph.replay()
+        if self.solver == 'captured':
+            return self.loss.detach(), self.preds
         if self.rebind:
             for p, g in self.grads:
                 p.grad = g

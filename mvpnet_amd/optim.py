@@ -10,23 +10,44 @@ instead of ATen's three multi_tensor_apply launches at the end of the training s
 (configs/scannet/unet_resnet34.yaml): momentum, dampening, Nesterov and weight decay in one launch per 124 tensors.
 `total_grad_norm` / `clip_grad_norm_` are nn.utils.clip_grad_norm_ (train_2d.py:181-185) as two launches per 240 tensors, without
 atomics or a host synchronisation, the same bits in every run; FusedSGD.step(grad_scale=coef) applies the clip coefficient while it reads
-the gradients, which then are never rewritten."""
+the gradients, which then are never rewritten.
+
+`FusedAdam(capturable=True)` + `DeviceMultiStepLR` (csrc/adam.hip: mvp_adam_advance_f32, mvp_adam_step_dev_f32, mvp_lr_multistep_f64) keep
+the step number and the learning rate on the device, so clip, step and schedule can be nodes of a captured training step
+(mvpnet3d.GraphedTrainStep(solver='captured')): every replay takes the next update at the scheduled rate.  Opt-in; nothing else changes."""
 import ctypes
 
 import torch
 
 from . import _lib as L
 
+HYPER_F32 = L.LIMITS['MVP_SOLVER_HYPER_F32']              # floats of a group's hyper block (mvp_adam_advance_f32)
+MILESTONE_SLOTS = L.LIMITS['MVP_SOLVER_MILESTONE_SLOTS']  # distinct milestones mvp_lr_multistep_f64 carries by value
+
 
 class FusedAdam(torch.optim.Adam):
+    """capturable=True: the step number and the learning rate live ON THE DEVICE (mvp_adam_advance_f32 + mvp_adam_step_dev_f32), so a
+    captured graph that holds step() takes update t + 1 at the current learning rate on every replay.  Then
+      * state[p]['step'] is a 0-dim float32 tensor on the parameter's device (torch's own capturable convention), the counts of a group
+        being views of one device buffer;
+      * group['lr'] stays a Python float for readers, but the LIVE value is device_lr(group_index), one device double per group, which
+        DeviceMultiStepLR multiplies in place; state_dict() reads it back into group['lr'] (a synchronisation point);
+      * materialize() creates every state and device value eagerly: call it before a capture, where the gradients step() will see exist;
+      * step(grad_scale=coef) multiplies every gradient by the device coefficient of total_grad_norm as the kernel reads it.
+    param_groups keep torch's `capturable: False`: state_dict() is what a plain torch.optim.Adam loads."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, **kwargs):
-        if amsgrad or kwargs.get('maximize') or kwargs.get('capturable') or kwargs.get('differentiable'):
-            raise ValueError('FusedAdam covers plain Adam (no amsgrad / maximize / capturable / differentiable)')
+        capturable = bool(kwargs.pop('capturable', False))
+        if amsgrad or kwargs.get('maximize') or kwargs.get('differentiable'):
+            raise ValueError('FusedAdam covers plain Adam (no amsgrad / maximize / differentiable)')
         kwargs.pop('fused', None)
         kwargs.pop('foreach', None)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, foreach=False, fused=False, **kwargs)
+        self.capturable = capturable
         self._plans = {}  # group index -> cached pointer arrays (parameters and moments do not move; gradients are re-read every step)
         self._step_bufs = {}  # group index -> (host buffer of the group's step counts, its 0-dim views = the states' 'step' tensors)
+        self._lr_buf = None  # capturable: (n_groups,) float64 on the device, the live learning rates
+        self._hyper = None  # capturable: (n_groups, MVP_SOLVER_HYPER_F32) float32 on the device, written by mvp_adam_advance_f32
 
     def _plan(self, gi, plist):
         key = tuple(id(p) for p in plist)
@@ -60,12 +81,180 @@ class FusedAdam(torch.optim.Adam):
         cache[0].add_(1.0)
         return cache[0].tolist()
 
+    # ---- capturable=True: counts, learning rates and bias corrections on the device ----
+    def _require_capturable(self, what):
+        if not self.capturable:
+            raise RuntimeError('FusedAdam.{} needs capturable=True'.format(what))
+
+    def _device_values(self):
+        """The live learning rates and the hyper blocks, created from group['lr'] (a host-to-device copy: never inside a capture)."""
+        n = len(self.param_groups)
+        if self._lr_buf is not None and self._lr_buf.numel() == n:
+            return self._lr_buf, self._hyper
+        devs = {p.device for g in self.param_groups for p in g['params']}
+        if len(devs) != 1 or next(iter(devs)).type != 'cuda':
+            raise RuntimeError('FusedAdam(capturable=True): all parameters must live on one GPU')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedAdam(capturable=True): call materialize() before the capture')
+        dev = next(iter(devs))
+        lr = torch.tensor([float(g['lr']) for g in self.param_groups], dtype=torch.float64).to(dev)
+        if self._lr_buf is not None:  # add_param_group: the earlier groups keep their live values
+            k = min(n, self._lr_buf.numel())
+            lr[:k].copy_(self._lr_buf[:k])
+        self._lr_buf, self._hyper = lr, torch.zeros(n, HYPER_F32, dtype=torch.float32, device=dev)
+        return self._lr_buf, self._hyper
+
+    def device_lr(self, group_index):
+        """The live learning rate of a group: a 0-dim float64 view of the device buffer (float() of it synchronises)."""
+        self._require_capturable('device_lr')
+        return self._device_values()[0][group_index]
+
+    def _new_state(self, p):
+        st = self.state[p]
+        st['step'] = torch.zeros((), dtype=torch.float32, device=p.device)
+        st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+    def _device_counts(self, gi, plist):
+        """The step counts of `plist` as ONE float32 device buffer whose 0-dim views are the states' 'step' tensors.  Found by identity, as
+        the host buffer of the plain mode; rebuilding it reads the counts back (so never inside a capture) and requires them equal: the
+        bias corrections of a launch come from the first."""
+        cache = self._step_bufs.get(gi)
+        state = self.state
+        if cache is not None and len(cache[1]) == len(plist) and all(state[p]['step'] is v for p, v in zip(plist, cache[1])):
+            return cache[0]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedAdam(capturable=True): the step counts of the parameters with gradients are not one device buffer yet: '
+                               'call materialize() before the capture, where those gradients exist')
+        dev = plist[0].device
+        base = torch.stack([state[p]['step'].detach().to(device=dev, dtype=torch.float32).reshape(()) for p in plist])
+        values = base.tolist()
+        if any(v != values[0] for v in values):
+            raise RuntimeError('FusedAdam(capturable=True): the parameters of a group that have gradients must have equal step counts '
+                               '(found {} to {}); use the non-capturable mode for such a state'.format(min(values), max(values)))
+        views = [base[i] for i in range(len(plist))]
+        for p, v in zip(plist, views):
+            state[p]['step'] = v
+        self._step_bufs[gi] = (base, views)
+        return base
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def materialize(self):
+        """capturable=True: creates, eagerly, what step() would create lazily -- moments and counts of EVERY parameter, the device learning
+        rates, and each group's count buffer over the parameters that have gradients now (over all of them when none has).  State created
+        inside a capture would be zeroed again by every replay, so step() refuses to create any there."""
+        self._require_capturable('materialize')
+        self._device_values()
+        for gi, group in enumerate(self.param_groups):
+            for p in group['params']:
+                if len(self.state[p]) == 0:
+                    self._check_param(p)
+                    self._new_state(p)
+            plist = [p for p in group['params'] if p.grad is not None] or list(group['params'])
+            if plist:
+                self._device_counts(gi, plist)
+
+    @staticmethod
+    def _check_param(p):
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) or (p.grad is not None and p.grad.is_sparse):
+            raise RuntimeError('FusedAdam: parameters must be dense contiguous float32 tensors on the GPU (use torch.optim.Adam otherwise)')
+
+    def _step_capturable(self, grad_scale):
+        if grad_scale is not None and not (torch.is_tensor(grad_scale) and grad_scale.is_cuda and grad_scale.dtype == torch.float32
+                                           and grad_scale.numel() == 1):
+            raise RuntimeError('FusedAdam: grad_scale must be a one-element float32 tensor on the GPU')
+        for gi, group in enumerate(self.param_groups):
+            plist = [p for p in group['params'] if p.grad is not None]
+            if not plist:
+                continue
+            dev = plist[0].device
+            for p in plist:
+                self._check_param(p)
+                if p.device != dev:
+                    raise RuntimeError('FusedAdam: the parameters of a group must live on one device')
+            if grad_scale is not None and grad_scale.device != dev:
+                raise RuntimeError('FusedAdam: grad_scale must live on the parameters\' device')
+            missing = [p for p in plist if len(self.state[p]) == 0]
+            if missing:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('FusedAdam(capturable=True): a parameter has no optimizer state yet and the stream is capturing (every '
+                                       'replay would zero it again): call materialize() before the capture')
+                for p in missing:
+                    self._new_state(p)
+            lr_buf, hyper = self._device_values()
+            counts = self._device_counts(gi, plist)
+            plan = self._plan(gi, plist)
+            grads = []
+            g_arr = plan['g']
+            for i, p in enumerate(plist):
+                g = p.grad
+                if g.dtype != torch.float32 or not g.is_contiguous():
+                    g = g.float().contiguous()
+                    grads.append(g)  # (kept alive until the launch is enqueued)
+                g_arr[i] = g.data_ptr()
+            beta1, beta2 = group['betas']
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                hyper_ptr = hyper.data_ptr() + gi * HYPER_F32 * 4
+                code = L._fn('mvp_adam_advance_f32')(counts.data_ptr(), len(plist), lr_buf.data_ptr() + gi * 8, float(beta1), float(beta2),
+                                                     hyper_ptr, stream)
+                if code != 0:
+                    L.check(code, 'mvp_adam_advance_f32')
+                code = L._fn('mvp_adam_step_dev_f32')(plan['p'], g_arr, plan['m'], plan['v'], plan['numel'], len(plist), hyper_ptr,
+                                                      None if grad_scale is None else grad_scale.data_ptr(), float(beta1), float(beta2),
+                                                      float(group['eps']), float(group['weight_decay']), stream)
+                if code != 0:
+                    L.check(code, 'mvp_adam_step_dev_f32')
+            del grads
+
+    def state_dict(self):
+        """capturable=True: the plain form -- `lr` a float read back from the device (into group['lr'] as well) and the counts as host
+        tensors --, so a torch.optim.Adam loads it.  A SYNCHRONISATION POINT: it waits for the stream."""
+        if not self.capturable:
+            return super().state_dict()
+        if self._lr_buf is not None and self._lr_buf.numel() == len(self.param_groups):
+            for group, lr in zip(self.param_groups, self._lr_buf.tolist()):
+                group['lr'] = lr
+        sd = super().state_dict()
+        keys = [k for k, v in sd['state'].items() if torch.is_tensor(v.get('step')) and v['step'].is_cuda]
+        if keys:
+            host = torch.stack([sd['state'][k]['step'].detach().reshape(()) for k in keys]).cpu()
+            for i, k in enumerate(keys):
+                sd['state'][k] = dict(sd['state'][k], step=host[i].clone())
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Takes the plain form (host counts, `lr` a float) and torch's capturable form (device counts) alike; capturable=True pushes the
+        learning rates and the counts to the device.  The group's count buffer is rebuilt -- and the counts required equal -- by the next
+        step() or materialize()."""
+        super().load_state_dict(state_dict)
+        if not self.capturable:
+            return
+        self._plans.clear()
+        self._step_bufs.clear()
+        for group in self.param_groups:
+            group['capturable'] = False  # (a checkpoint of torch's capturable Adam says True: the flag of this class is self.capturable)
+            for p in group['params']:
+                st = self.state.get(p)
+                if st and 'step' in st:
+                    st['step'] = torch.as_tensor(st['step'], dtype=torch.float32).detach().reshape(()).to(p.device)
+        self._lr_buf = None
+        if any(p.is_cuda for g in self.param_groups for p in g['params']):
+            self._device_values()
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=None):
+        """grad_scale (capturable=True only): None, or a one-element float32 tensor on the parameters' device (the `coef` of
+        total_grad_norm): every gradient is multiplied by it as the kernel reads it; the gradients themselves stay unscaled."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.capturable:
+            self._step_capturable(grad_scale)
+            return loss
+        if grad_scale is not None:
+            raise ValueError('FusedAdam: grad_scale needs capturable=True (mvp_adam_step_f32 takes no scale)')
         for gi, group in enumerate(self.param_groups):
             plist = [p for p in group['params'] if p.grad is not None]
             if not plist:
@@ -113,6 +302,77 @@ class FusedAdam(torch.optim.Adam):
                         L.check(code, 'mvp_adam_step_f32')
             del grads
         return loss
+
+
+def multistep_table(milestones, gamma):
+    """-> (the distinct milestones, ascending; gamma ** multiplicity of each): the host half of MultiStepLR, whose chainable form multiplies
+    the learning rate by gamma ** milestones[epoch] (a Counter) when it reaches a milestone."""
+    from collections import Counter
+    count = Counter(int(m) for m in milestones)
+    distinct = sorted(count)
+    return distinct, [float(gamma) ** count[m] for m in distinct]
+
+
+class DeviceMultiStepLR:
+    """torch.optim.lr_scheduler.MultiStepLR on the DEVICE learning rates of a capturable FusedAdam: step() is one launch
+    (mvp_lr_multistep_f64) that counts the epoch and multiplies the rates in the doubles torch uses, so a captured graph that holds it
+    follows the schedule on every replay.  Nothing is written to param_groups: the optimizer's state_dict() reads the rates back.
+    last_epoch=-1 starts at epoch 0 with the optimizer's current rates; a resumed last_epoch takes the current rates as they are, as
+    torch does.  `last_epoch` reads the device counter (a synchronisation point)."""
+
+    def __init__(self, optimizer, milestones, gamma=0.1, last_epoch=-1):
+        from collections import Counter
+        if not (isinstance(optimizer, FusedAdam) and optimizer.capturable):
+            raise ValueError('DeviceMultiStepLR drives a FusedAdam(capturable=True): its learning rates live on the device')
+        self.optimizer = optimizer
+        self.milestones = Counter(int(m) for m in milestones)
+        self.gamma = gamma
+        if last_epoch == -1:
+            for group in optimizer.param_groups:
+                group.setdefault('initial_lr', group['lr'])
+        elif any('initial_lr' not in g for g in optimizer.param_groups):
+            raise KeyError("param 'initial_lr' is not specified in param_groups when resuming an optimizer")
+        self.base_lrs = [g['initial_lr'] for g in optimizer.param_groups]
+        self._table()
+        lr_buf, _ = optimizer._device_values()
+        self._epoch = torch.tensor([0 if last_epoch == -1 else int(last_epoch)], dtype=torch.int64).to(lr_buf.device)
+
+    def _table(self):
+        distinct, factors = multistep_table(self.milestones.elements(), self.gamma)
+        if len(distinct) > MILESTONE_SLOTS:
+            raise ValueError('DeviceMultiStepLR holds {} distinct milestones, not {}'.format(MILESTONE_SLOTS, len(distinct)))
+        n = len(distinct)
+        self._args = ((ctypes.c_int64 * n)(*distinct), (ctypes.c_double * n)(*factors), n)
+
+    @property
+    def last_epoch(self):
+        return int(self._epoch.item())
+
+    def step(self):
+        lr_buf, _ = self.optimizer._device_values()
+        dev = lr_buf.device
+        with torch.cuda.device(dev):
+            code = L._fn('mvp_lr_multistep_f64')(self._epoch.data_ptr(), lr_buf.data_ptr(), lr_buf.numel(), self._args[0], self._args[1],
+                                                 self._args[2], torch.cuda.current_stream(dev).cuda_stream)
+        if code != 0:
+            L.check(code, 'mvp_lr_multistep_f64')
+
+    def get_last_lr(self):
+        """-> the live rates, 0-dim float64 device views (one per group)."""
+        return [self.optimizer.device_lr(i) for i in range(len(self.optimizer.param_groups))]
+
+    def state_dict(self):
+        return {'last_epoch': self.last_epoch, 'milestones': self.milestones, 'gamma': self.gamma, 'base_lrs': list(self.base_lrs)}
+
+    def load_state_dict(self, state_dict):
+        """Takes its own form and a torch MultiStepLR.state_dict() of the same schedule; the learning rates are the optimizer's."""
+        from collections import Counter
+        milestones = Counter({int(k): int(v) for k, v in dict(state_dict['milestones']).items()})
+        if milestones != self.milestones or state_dict['gamma'] != self.gamma:
+            raise ValueError('DeviceMultiStepLR.load_state_dict: another schedule (milestones {} gamma {}) than this one ({} / {})'.format(
+                sorted(milestones.elements()), state_dict['gamma'], sorted(self.milestones.elements()), self.gamma))
+        self.base_lrs = list(state_dict['base_lrs'])
+        self._epoch.copy_(torch.tensor([int(state_dict['last_epoch'])], dtype=torch.int64))
 
 
 SGD_TENSORS_PER_LAUNCH = 124      # (csrc/solver.hip: kSgdMax)
