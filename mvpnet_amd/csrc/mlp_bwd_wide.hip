@@ -23,7 +23,8 @@
 // dW stays in accumulator registers for the whole kernel (2 tiles of 32 x 32 per wave) and is flushed once per workgroup.
 // Traffic: 2 C_i + 2 C_{i-1} floats per row.  LDS: W image 68 KB + dy 34 KB + a 34 KB (2 pieces) = 136 KB: one workgroup per CU, 2 waves
 // per SIMD; tiles are handed out through a ticket so that a CU that is busy with another stream's workgroup (the sampler holds 16 CUs
-// for a millisecond beside the backward pass) costs its share of the tiles, not a second round.
+// for a millisecond beside the backward pass) costs its share of the tiles, not a second round.  The 64-channel instances take their tiles
+// in RUNS of consecutive tiles per ticket draw and run one workgroup per CU: kWideResidency and the tile loop say why.
 #include "mlp_common.h"
 #include "dropout.h"
 #include <algorithm>
@@ -60,13 +61,35 @@ struct WideArgs {
   float* ws;             // nullptr: fp32 atomics; else this launch's partial tiles (dw_reduce_kernel<4, 4> adds them in order)
   float* dZ;             // (R, Cp)
   double* stat_prev;     // (2 Cp) accumulated into (fp64 atomics, one per column and workgroup); nullptr without act
-  int* ticket;           // zero on entry: tiles beyond the first of each workgroup are taken by ticket; nullptr: static round-robin
+  int* ticket;           // zero on entry: tiles beyond the first RUN of each workgroup are taken by ticket; nullptr: static round-robin
+  int run;               // with a ticket: consecutive tiles per draw (>= 1)
   int64_t R;
   int C, Cp, ntiles;
   // DWO instances (weight gradient only, a (c_out block, c_in block) pair of 128 x 128 per blockIdx.y): C / Cp are the WHOLE layer's widths
   // on entry, ldg the row stride of G / Yi (= the whole C), nbb the number of c_in blocks
   int ldg, nbb;
 };
+
+// ---- Residency: workgroups per CU of the shipped 64-channel instances, {pieces NS, MODE, CH, workgroups per CU}.  ONE table: the launch
+// bounds and the launcher's grid read it, tests/test_bwd_wide_regs_cpu.py checks it against the built code objects, tools/residency.py
+// prints what the compiler gave.  A workgroup is 8 waves = 2 per SIMD, so two workgroups share a CU only at 4 waves per SIMD: at most 128
+// registers (VGPR + AGPR) per lane without scratch, and 2 x the LDS within 160 KB (58 KB at two pieces; 83 KB at three: bf16x6 is bound to one).
+// Every instance is at ONE: the mode-1 / mode-3 instances hold 142 - 161 registers, so the 2 x CUs workgroups that used to be launched ran
+// one per CU with the second half waiting for a spent ticket (8 us per launch for their W images and dW flushes).  Brought to 117 - 126
+// registers -- one accumulator tile per wave role, column constants re-read from LDS per row, scalar tile bases -- two resident workgroups
+// measured 158 us (mode 1) and 137 us (mode 3) against 147 and 141 us for one per CU with the register budget left alone
+// (profiles/bwd_wide_ch64_residency.txt): no gain beyond the spread, so none ships at two.  An entry set to 2 must meet the budget.
+struct WideResidency { int ns, mode, ch, per_cu; };
+constexpr WideResidency kWideResidency[] = {
+  {1, 0, 64, 1}, {1, 1, 64, 1}, {1, 2, 64, 1}, {1, 3, 64, 1},
+  {2, 0, 64, 1}, {2, 1, 64, 1}, {2, 2, 64, 1}, {2, 3, 64, 1},
+  {3, 0, 64, 1}, {3, 1, 64, 1}, {3, 2, 64, 1}, {3, 3, 64, 1},
+};
+constexpr int wide_per_cu(int ns, int mode, int ch) {  // (not listed -- MODE -1, CH = 128: one)
+  for (const WideResidency& w : kWideResidency)
+    if (w.ns == ns && w.mode == mode && w.ch == ch) return w.per_cu;
+  return 1;
+}
 
 __device__ __forceinline__ uint2 lds_tr16(const unsigned char* p) {  // ds_read_b64_tr_b16: lane p of a 16-lane group supplies 8 bytes, gets column p of the 4 x 16 block
   typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -91,14 +114,14 @@ struct TileRegs {  // one thread's 16-byte pieces of a tile: rows rbase + RPP j 
 // kernel).  MODE == -1: everything decided at run time (narrower layers, plain inputs: tests and odd networks).
 // CH = 128 or 64: the channel capacity of the instance (row pieces, images and the MFMA tiling follow it).  CH = 64 is the shape of the
 // aggregation MLP's inner layers (786 432 rows x 64 -> 64): 16 pieces per row, 32 rows per pass of the 512 threads, waves 0 - 3 take the four
-// dX tiles and waves 4 - 7 the four dW tiles; 58 KB of LDS.
+// dX tiles and waves 4 - 7 the four dW tiles; 58 KB of LDS, one workgroup per CU (kWideResidency).
 // DWO: the weight gradient ALONE, dW (C, Cp) += dy^T . a for layers of any width, in (128 c_out) x (128 c_in) blocks: blockIdx.y names the
 // block, the workgroups of a block share its row tiles round-robin, P1 + P2b of the tile loop run as they are (16-byte row pieces -> bf16 images ->
 // transpose reads -> MFMA) and everything that belongs to dX is compiled out (no W image, no P2a / P3 / P4, no column sums).  Replaces
 // mlp_dw_bf_kernel (4-byte operand loads, 64 x 64 blocks: every operand re-read twice as often) for the 256- / 512-wide layers behind
 // mvp_mlp_weight_grad_f32 and its finish-on-load form (MODE 0: G is dy; 1: G is dz, the finish happens in P1).
 template <int NS, int MODE, int CH, bool DWO = false>
-__global__ __launch_bounds__(kWT, 2) void mlp_bwd_wide_kernel(WideArgs pin) {
+__global__ __launch_bounds__(kWT, (!DWO && wide_per_cu(NS, MODE, CH) == 2) ? 4 : 2) void mlp_bwd_wide_kernel(WideArgs pin) {
   WideArgs p = pin;
   if constexpr (DWO) {
     const int ab = (int)blockIdx.y / p.nbb, bb = (int)blockIdx.y - ab * p.nbb;
@@ -177,8 +200,14 @@ __global__ __launch_bounds__(kWT, 2) void mlp_bwd_wide_kernel(WideArgs pin) {
     for (int j = 0; j < NJ; ++j) t.x[j] = *reinterpret_cast<const f32x4*>(Xt + (clamp ? min(rbase + RPP * j, tail_rows - 1) * p.ldx + (xok ? cc : 0) : offx[j]));
   };
   TileRegs<NJ> ta;
-  int cur = (int)blockIdx.x;
-  if (tid == 0) misc[0] = p.ticket ? step + atomicAdd(p.ticket, 1) : cur + step;
+  // With a ticket the tiles are handed out in RUNS of `run` consecutive tiles: a workgroup's first run is static (blockIdx.x), every later one
+  // is named by a draw.  One draw per TILE made the ticket the kernel's clock at 64 channels: every draw of every workgroup is a returning
+  // atomic on one address, they complete ~15 ns apart, and the 12 288 tiles of 786 432 rows x 15 ns are the 181 - 190 us the CH = 64 kernel
+  // took whatever its mode, precision or grid, while the static order ran the same tiles in 125 - 160 us (profiles/bwd_wide_ch64_residency.txt).
+  const int run = p.ticket ? p.run : 1;
+  int cur = (int)blockIdx.x * run;
+  int nleft = run > 1 ? run - 2 : 0;  // tiles of its run behind tile `nxt`
+  if (tid == 0) misc[0] = p.ticket ? (run > 1 ? cur + 1 : step + atomicAdd(p.ticket, 1)) : cur + step;
   if (cur < ntiles) {  // in flight under the staging of the W image
     load_gy(ta, cur);
     load_x(ta, cur);
@@ -268,7 +297,8 @@ __global__ __launch_bounds__(kWT, 2) void mlp_bwd_wide_kernel(WideArgs pin) {
     // The ticket for the tile after next is requested FIRST and consumed last (behind P1): a returning atomic counts in vmcnt like a load and
     // returns in order, so waiting for one issued BEHIND this tile's prefetches would drain them all (~2 us of exposed latency per tile)
     int tk = 0;
-    if (tid == 0 && p.ticket) tk = atomicAdd(p.ticket, 1);
+    const bool draw = nleft == 0;  // `nxt` closes its run: the tile behind it opens the run that the ticket names
+    if (tid == 0 && p.ticket && draw) tk = atomicAdd(p.ticket, 1);
     const int nload = min(nxt, ntiles - 1);  // the prefetches below are UNCONDITIONAL (a load inside a branch makes the compiler wait for everything
                                              // outstanding at the join); past the last tile they re-read it and nobody uses the values
     const bool tail = cur == ntiles - 1 && tail_rows < kTR;
@@ -398,7 +428,8 @@ __global__ __launch_bounds__(kWT, 2) void mlp_bwd_wide_kernel(WideArgs pin) {
       }
     };
     if (tail) p1(std::true_type{}); else p1(std::false_type{});
-    if (tid == 0) misc[(it + 1) & 1] = p.ticket ? step + tk : nxt + step;
+    if (tid == 0) misc[(it + 1) & 1] = p.ticket ? (draw ? (step + tk) * run : nxt + 1) : nxt + step;
+    nleft = draw ? run - 1 : nleft - 1;
     WIDE_T(1);
     __syncthreads();
     WIDE_T(2);
@@ -638,15 +669,19 @@ MVP_API int mvp_mlp_layer_backward_wide_pooled_p_f32(const float* G, const float
     return n > 0 ? n : 256;
   }();
   const int cb_host = (C <= 64 && Cp <= 64) ? 2 : 4;  // 32-column blocks of the instance that runs (CH = 64 / 128)
-  // (CH = 64: 58 KB of LDS per workgroup -- two fit a CU when their registers do; the ticket makes a surplus workgroup harmless)
-  const int grid = std::min(a.ntiles, cb_host == 2 ? 2 * cus : cus);
+  // CH = 64 instances for layers with at most 64 channels on both sides (the aggregation MLP's inner layers), CH = 128 otherwise
+  const int ch = (C <= 64 && Cp <= 64) ? 64 : kWCh;
+  const bool fast = C == ch && Cp == ch && act_mean != nullptr && (ldw & 3) == 0 && ((uintptr_t)W & 15) == 0;
+  const int inst_mode = !fast ? -1 : mode == 0 ? 0 : mode == 1 ? 1 : pool_k > 1 ? 3 : 2;  // the MODE of the instance that runs
+  // the grid is what is resident: as many workgroups per CU as kWideResidency gives the instance (one for all of them today)
+  const int grid = std::min(a.ntiles, wide_per_cu(ns, inst_mode, ch) * cus);
   // reproducible mode: partial tiles through the workspace + ordered reduction, and a STATIC tile order (the ticket would make a
   // workgroup's share, hence the order of its fp32 additions, differ from run to run)
   a.ws = (workspace && grid > 1 && (int64_t)grid * cb_host * cb_host * 1024 <= workspace_floats) ? workspace : nullptr;
   a.ticket = a.ws ? nullptr : ticket;
-  // CH = 64 instances for layers with at most 64 channels on both sides (the aggregation MLP's inner layers), CH = 128 otherwise
-  const int ch = (C <= 64 && Cp <= 64) ? 64 : kWCh;
-  const bool fast = C == ch && Cp == ch && act_mean != nullptr && (ldw & 3) == 0 && ((uintptr_t)W & 15) == 0;
+  // Tiles per ticket draw (CH = 64; the 128-wide instances, half as many tiles per byte, keep one): 2 - 4 once a workgroup has 32 or more
+  // tiles to take, which still leaves it 16 or more draws to even out a CU that another stream keeps busy.  786 432 rows on 256 CUs: 3.
+  a.run = (ch == 64 && a.ticket) ? std::max(1, std::min(4, a.ntiles / grid / 16)) : 1;
   const size_t row_b = (size_t)ch * 2 + 16;
   const size_t ldsz = std::max<size_t>((size_t)ns * (ch * row_b + 2 * kTR * row_b) + 64 + 11 * (size_t)ch * 4, (size_t)2 * (kWT / (ch / 4)) * ch * 8);
 #define MVP_WIDE_LAUNCH(NS_, MODE_, CH_)                                                                                       \
@@ -658,11 +693,11 @@ MVP_API int mvp_mlp_layer_backward_wide_pooled_p_f32(const float* G, const float
   } while (0)
 #define MVP_WIDE_MODES(NS_, CH_)                          \
   do {                                                    \
-    if (!fast) MVP_WIDE_LAUNCH(NS_, -1, CH_);             \
-    else if (mode == 0) MVP_WIDE_LAUNCH(NS_, 0, CH_);     \
-    else if (mode == 1) MVP_WIDE_LAUNCH(NS_, 1, CH_);     \
-    else if (pool_k > 1) MVP_WIDE_LAUNCH(NS_, 3, CH_);    \
-    else MVP_WIDE_LAUNCH(NS_, 2, CH_);                    \
+    if (inst_mode < 0) MVP_WIDE_LAUNCH(NS_, -1, CH_);      \
+    else if (inst_mode == 0) MVP_WIDE_LAUNCH(NS_, 0, CH_); \
+    else if (inst_mode == 1) MVP_WIDE_LAUNCH(NS_, 1, CH_); \
+    else if (inst_mode == 3) MVP_WIDE_LAUNCH(NS_, 3, CH_); \
+    else MVP_WIDE_LAUNCH(NS_, 2, CH_);                     \
   } while (0)
   if (ns == 3) MVP_WIDE_MODES(3, 64);
   else if (ns == 1 && ch == 64) MVP_WIDE_MODES(1, 64);
@@ -697,7 +732,7 @@ int mlp_dw_wide_launch(const float* G, const float* Yi, const float* mean_i, con
   a.inv_rows = inv_rows;
   a.mode = Yi ? 1 : 0; a.gk = 1; a.drop = Dropout{0u, 0u, 1.0f};
   a.X = X; a.ldx = (int)ldx; a.act = InAct{act_mean, act_invstd, act_gamma, act_beta};
-  a.W = nullptr; a.ldw = 0; a.dW = dW; a.lddw = (int)lddw; a.ws = nullptr; a.dZ = nullptr; a.stat_prev = nullptr; a.ticket = nullptr;
+  a.W = nullptr; a.ldw = 0; a.dW = dW; a.lddw = (int)lddw; a.ws = nullptr; a.dZ = nullptr; a.stat_prev = nullptr; a.ticket = nullptr; a.run = 1;
   a.R = R; a.C = (int)C; a.Cp = (int)Cp; a.ntiles = (int)cdiv(R, kTR);
   a.ldg = (int)C; a.nbb = (int)(Cp / kWCh);
   static const int cus = []() {
