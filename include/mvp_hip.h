@@ -293,6 +293,35 @@ int mvp_lift_store_f32(const void* depth, int depth_is_u16, const float* kinv, c
                        const float* box, const float* points, const float* store, const int32_t* view_slot, int64_t U,
                        int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace,
                        int64_t* knn_index, float* gfeature, float* gxyz, mvp_stream_t stream);
+/* ---- lifting from 16-bit feature maps and stores: the rows are widened in the gather, no float32 copy is made ----
+ * The four entries below are their `_f32` siblings with the feature map / store as `const void*` followed by `int feature_type`
+ * (the `depth, depth_is_u16` convention): bfloat16 or float16 elements, 16-byte aligned (else MVP_EINVAL); any other feature_type is
+ * MVP_EINVAL.  Everything else -- the other inputs, the shape limits, the checks, the outputs, `float* gfeature` included -- is the
+ * sibling's.  Widening bfloat16 / float16 to float32 is exact (subnormals, infinities and signed zeros included), so the results do not
+ * depend on where it happens.  Forward only: there is no backward entry for a 16-bit map. */
+#define MVP_FEATURE_BF16 1
+#define MVP_FEATURE_F16 2
+/* mvp_lift_gather_f32 on a 16-bit feature (B,P,C): bit-equal to the `_f32` entry on the exactly widened copy.  C % 4 != 0 is served
+ * (one element per lane), as there. */
+int mvp_lift_gather_h16(const void* feature, int feature_type, const float* image_xyz, const int64_t* index, int64_t B, int64_t P,
+                        int64_t C, int64_t N, int64_t k, float* gfeature, float* gxyz, mvp_stream_t stream);
+/* mvp_lift_f32 on a 16-bit feature (B,nv,h,w,C), C % 4 == 0: bit-equal to the `_f32` entry on the exactly widened copy. */
+int mvp_lift_h16(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                 const float* box, const float* points, const void* feature, int feature_type, int64_t B, int64_t nv, int64_t h,
+                 int64_t w, int64_t N, int64_t C, int64_t k, void* workspace, int64_t* knn_index, float* gfeature,
+                 float* gxyz, float* image_xyz, uint8_t* mask, mvp_stream_t stream);
+/* mvp_lift_aug_f32 on a 16-bit feature (B,nv,h,w,C), C % 4 == 0: bit-equal to the `_f32` entry on the exactly widened copy. */
+int mvp_lift_aug_h16(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                     const float* box, const float* points, const void* feature, int feature_type, int64_t B, int64_t nv, int64_t h,
+                     int64_t w, int64_t N, int64_t C, int64_t k, void* workspace, int64_t* knn_index, float* gfeature,
+                     float* gxyz, float* image_xyz, uint8_t* mask, const uint8_t* flip, const double* rot, float* points_out,
+                     mvp_stream_t stream);
+/* mvp_lift_store_f32 on a 16-bit store (U,h,w,C), C % 4 == 0: bit-equal to the `_f32` entry on the exactly widened copy.  A given
+ * number of bytes holds twice the frames. */
+int mvp_lift_store_h16(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                       const float* box, const float* points, const void* store, int feature_type, const int32_t* view_slot,
+                       int64_t U, int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace,
+                       int64_t* knn_index, float* gfeature, float* gxyz, mvp_stream_t stream);
 /* out[b,r,:] = float32( rot[b] (float64 3x3) . xyz[b,r,:] ), rows R per batch element: the z-rotation augmentation of `points`
  * / `image_xyz` (scannet_2d3d.py:400-409) for tensors that did not go through mvp_lift_aug_f32.  In place allowed. */
 int mvp_rotate_rows_f32(const float* xyz, const double* rot, int64_t B, int64_t R, float* out, mvp_stream_t stream);

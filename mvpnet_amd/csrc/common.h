@@ -51,4 +51,19 @@ __device__ __forceinline__ double shfl_xor_t<double>(double v, int m) {
 // gfx950 (back-off barriers: the ticket could otherwise be performed while another channel still queues this lane's adds).
 __device__ __forceinline__ void wait_vm_complete() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// 16-bit feature rows (MVP_FEATURE_BF16 / MVP_FEATURE_F16) widened to float32 in registers.  Both widenings are exact for every value:
+// bfloat16 is the upper half of the float32 pattern (an integer shift: no arithmetic touches the value, subnormals keep their bits);
+// float16 goes through the hardware conversion, which takes subnormal halves as they are (f16 denormals are never flushed on gfx9) and
+// whose results are all normal float32 numbers.  `lo` = the element in bits 0..15 of the word, `hi` = the one in bits 16..31.
+template <bool F16>
+__device__ __forceinline__ float widen_h16_lo(unsigned w) {
+  if constexpr (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
+  else return __uint_as_float(w << 16);
+}
+template <bool F16>
+__device__ __forceinline__ float widen_h16_hi(unsigned w) {
+  if constexpr (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
+  else return __uint_as_float(w & 0xffff0000u);
+}
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -521,6 +521,38 @@ __device__ __forceinline__ void gather_rows(const float4* fb, float4* ob, const 
   }
 }
 
+// gather_rows for 16-bit feature rows (bfloat16 / float16): same sidx, same row-per-lane layout, same rows in flight, same non-temporal
+// full-line float32 stores.  The load is 8 bytes per lane (4 channels; C = 64: 16 lanes x 8 B = one 128-byte line per row) and is widened
+// in registers (common.h: exact for every value), so the rows written equal gather_rows' on the widened copy bit for bit.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+template <int T, bool F16>
+__device__ __forceinline__ void gather_rows_h16(const u32x2* fb, float4* ob, const int* sidx, int rows, int C, int tid) {
+  const int C4 = C >> 2;      // C % 4 == 0 checked by the host entry
+  const int rpp = T / C4;     // rows per pass
+  const int c4 = tid % C4, r0 = tid / C4;
+  constexpr int U = MVP_GATHER_U;  // rows in flight per lane
+  for (int r = r0; r < rows; r += rpp * U) {
+    u32x2 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u * rpp;
+      v[u] = u32x2{0u, 0u};  // (+0 in either type)
+      if (rr < rows) {
+        const int id = sidx[rr];
+        if (id >= 0) v[u] = fb[(size_t)id * C4 + c4];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u * rpp;
+      if (rr < rows) {
+        const f32x4 o = {widen_h16_lo<F16>(v[u].x), widen_h16_hi<F16>(v[u].x), widen_h16_lo<F16>(v[u].y), widen_h16_hi<F16>(v[u].y)};
+        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(ob + (size_t)rr * C4 + c4));
+      }
+    }
+  }
+}
+
 #ifndef MVP_LIFT_WAVES
 #define MVP_LIFT_WAVES 1
 #endif
@@ -712,6 +744,138 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MVP_LIFT_WAVE
                     min(T, N - blk * T) * K, C, tid);
 }
 
+// The two kernels above for 16-bit feature rows (mvp_lift_h16 / mvp_lift_aug_h16: STORE = false; mvp_lift_store_h16: STORE = true).
+// `feature` is the (B,nv,h,w,C) map, or the (U,h,w,C) store, of bfloat16 or float16 elements; feature_type (MVP_FEATURE_*, uniform over
+// the launch) picks the widening inside the one instance per (K, T).  Placement, search, flip, rotation, the slot table, sidx and the
+// zero rows are the code of the float32 kernels; only the gather reads half the bytes (gather_rows_h16).  gfeat stays float32.
+// __global__s of their own: the float32 instances keep their names and their code.
+template <int K, int T, bool STORE>
+__device__ __forceinline__ void lift_knn_gather_h16(const float4* __restrict__ rec, const uint16_t* __restrict__ plane, int pitch,
+                                                    const float* __restrict__ points, const float* __restrict__ cam,
+                                                    const float* __restrict__ pose, const uint16_t* __restrict__ feature, int feature_type,
+                                                    const int* __restrict__ view_slot, int U, int B, int nv, int h, int w, int N, int C,
+                                                    int bpc, int64_t* __restrict__ knn_index, float* __restrict__ gfeat,
+                                                    float* __restrict__ gxyz, const uint8_t* __restrict__ flip,
+                                                    const double* __restrict__ rot, float* __restrict__ points_out) {
+  __shared__ ViewParam vp[kMaxViews];
+  __shared__ int vslot[STORE ? kMaxViews : 1];
+  __shared__ int sidx[T * K];
+  __shared__ int slist[T * kSurvCap];
+  const int L = blockIdx.x;  // XCD-aware chunk placement, as above
+  int b, blk;
+  if (B >= kXcds) {
+    const int xcd = L % kXcds, jb = L / kXcds;
+    b = xcd + kXcds * (jb / bpc);
+    blk = jb % bpc;
+  } else {
+    b = L / bpc;
+    blk = L - b * bpc;
+  }
+  if (b >= B) return;  // uniform per workgroup
+  const int tid = threadIdx.x;
+  if (tid < nv) {
+    vp[tid] = make_view_param(cam + ((size_t)b * nv + tid) * 9, pose + ((size_t)b * nv + tid) * 16, h, w);
+    if constexpr (STORE) {
+      const int slot = view_slot[(size_t)b * nv + tid];
+      vslot[tid] = (slot >= 0 && slot < U) ? slot : -1;
+    }
+  }
+  __syncthreads();
+
+  const int hw = h * w;
+  const int P = nv * hw;
+  const float4* crec = rec + (size_t)b * P;
+  const int n = blk * T + tid;
+  const bool active = n < N;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) {
+    const float* q = points + ((size_t)b * N + n) * 3;
+    qx = q[0]; qy = q[1]; qz = q[2];
+  }
+  unsigned long long kk[K];
+  filtered_search<K, T>(crec, plane + (size_t)b * nv * plane_rows(h) * pitch, vp, nv, h, w, pitch, active, qx, qy, qz, kk, slist, tid);
+  if (active) {
+    double r0 = 1, r1 = 0, r2 = 0, r3 = 0, r4 = 1, r5 = 0, r6 = 0, r7 = 0, r8 = 1;
+    if (!STORE && rot) {
+      const double* Rm = rot + (size_t)b * 9;
+      r0 = Rm[0]; r1 = Rm[1]; r2 = Rm[2]; r3 = Rm[3]; r4 = Rm[4]; r5 = Rm[5]; r6 = Rm[6]; r7 = Rm[7]; r8 = Rm[8];
+    }
+    auto rotate = [&](float x, float y, float z, float* o) {  // float64 product, one rounding to float32 (lift_knn_gather_kernel)
+      if (!STORE && rot) {
+        const double dx = x, dy = y, dz = z;
+        o[0] = (float)((r0 * dx + r1 * dy) + r2 * dz);
+        o[1] = (float)((r3 * dx + r4 * dy) + r5 * dz);
+        o[2] = (float)((r6 * dx + r7 * dy) + r8 * dz);
+      } else {
+        o[0] = x; o[1] = y; o[2] = z;
+      }
+    };
+    if (!STORE && points_out) rotate(qx, qy, qz, points_out + ((size_t)b * N + n) * 3);
+    float4 wrec[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {  // the winners' coordinates: K independent loads
+      const bool found = kk[s] != ~0ull;
+      wrec[s] = (gxyz && found) ? crec[(int)(unsigned)kk[s]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      const bool found = kk[s] != ~0ull;
+      const int id = found ? (int)(unsigned)kk[s] : -1;
+      int oid = id;  // what knn_index holds: the chunk-local id, in the (possibly mirrored) public pixel order
+      int row = id;  // the row of `feature` the neighbour copies, negative = a zero row
+      if constexpr (STORE) {
+        row = -1;  // U * hw < 2^31 checked by the host entry
+        if (found) {
+          const int vi = id / hw;
+          const int slot = vslot[vi];
+          row = slot >= 0 ? slot * hw + (id - vi * hw) : -1;
+        }
+      } else {
+        if (flip && found) {
+          const int vi = id / hw, rem = id - vi * hw;
+          if (flip[(size_t)b * nv + vi]) {
+            const int vv = rem / w, uu = rem - vv * w;
+            oid = vi * hw + vv * w + (w - 1 - uu);
+          }
+        }
+        row = oid;
+      }
+      sidx[tid * K + s] = row;
+      knn_index[((size_t)b * N + n) * K + s] = (int64_t)oid;
+      if (gxyz) {
+        float* o = gxyz + (((size_t)b * N + n) * K + s) * 3;
+        if (found) rotate(wrec[s].x, wrec[s].y, wrec[s].z, o); else { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; }
+      }
+    }
+  }
+  if (!gfeat) return;
+  __syncthreads();
+  const u32x2* fb = reinterpret_cast<const u32x2*>(STORE ? feature : feature + (size_t)b * P * C);
+  float4* ob = reinterpret_cast<float4*>(gfeat + ((size_t)b * N + (size_t)blk * T) * K * C);
+  const int rows = min(T, N - blk * T) * K;
+  if (feature_type == MVP_FEATURE_F16) gather_rows_h16<T, true>(fb, ob, sidx, rows, C, tid);
+  else gather_rows_h16<T, false>(fb, ob, sidx, rows, C, tid);
+}
+
+template <int K, int T>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MVP_LIFT_WAVES))) void lift_knn_gather_h16_kernel(
+    const float4* __restrict__ rec, const uint16_t* __restrict__ plane, int pitch, const float* __restrict__ points, const float* __restrict__ cam,
+    const float* __restrict__ pose, const uint16_t* __restrict__ feature, int feature_type, int B, int nv, int h, int w, int N, int C, int bpc,
+    int64_t* __restrict__ knn_index, float* __restrict__ gfeat, float* __restrict__ gxyz, const uint8_t* __restrict__ flip,
+    const double* __restrict__ rot, float* __restrict__ points_out) {
+  lift_knn_gather_h16<K, T, false>(rec, plane, pitch, points, cam, pose, feature, feature_type, nullptr, 0, B, nv, h, w, N, C, bpc, knn_index, gfeat,
+                                   gxyz, flip, rot, points_out);
+}
+
+template <int K, int T>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MVP_LIFT_WAVES))) void lift_knn_gather_store_h16_kernel(
+    const float4* __restrict__ rec, const uint16_t* __restrict__ plane, int pitch, const float* __restrict__ points, const float* __restrict__ cam,
+    const float* __restrict__ pose, const uint16_t* __restrict__ store, int feature_type, const int* __restrict__ view_slot, int U, int B, int nv,
+    int h, int w, int N, int C, int bpc, int64_t* __restrict__ knn_index, float* __restrict__ gfeat, float* __restrict__ gxyz) {
+  lift_knn_gather_h16<K, T, true>(rec, plane, pitch, points, cam, pose, store, feature_type, view_slot, U, B, nv, h, w, N, C, bpc, knn_index, gfeat,
+                                  gxyz, nullptr, nullptr, nullptr);
+}
+
 // one-wave workgroups while the launch has fewer than 4 workgroups of 256 points per CU (a few dense chunks, a single chunk's latency);
 // MVP_LIFT_WG = 64 / 256 forces one shape (A/B switch).  The gather needs T % (C / 4) == 0.
 inline bool lift_small_workgroups(int64_t B, int64_t N, int64_t C) {
@@ -765,6 +929,41 @@ int launch_lift(const float4* rec, const uint16_t* plane, int pitch, const float
   if (lift_small_workgroups(B, N, C))
     return launch_lift_t<K, 64>(rec, plane, pitch, points, cam, pose, feature, B, nv, h, w, N, C, knn_index, gfeat, gxyz, flip, rot, points_out, s);
   return launch_lift_t<K, kLFThreads>(rec, plane, pitch, points, cam, pose, feature, B, nv, h, w, N, C, knn_index, gfeat, gxyz, flip, rot, points_out, s);
+}
+
+// The 16-bit launchers: view_slot == nullptr = the map of mvp_lift_h16 / mvp_lift_aug_h16, else the store of mvp_lift_store_h16.
+template <int K, int T>
+int launch_lift_h16_t(const float4* rec, const uint16_t* plane, int pitch, const float* points, const float* cam, const float* pose,
+                      const uint16_t* feature, int feature_type, const int* view_slot, int64_t U, int64_t B, int64_t nv, int64_t h, int64_t w,
+                      int64_t N, int64_t C, int64_t* knn_index, float* gfeat, float* gxyz, const uint8_t* flip, const double* rot,
+                      float* points_out, hipStream_t s) {
+  const int bpc = (int)cdiv(N, T);
+  if (view_slot)
+    hipLaunchKernelGGL((lift_knn_gather_store_h16_kernel<K, T>), lift_grid(B, bpc), dim3(T), 0, s, rec, plane, pitch, points, cam, pose, feature,
+                       feature_type, view_slot, (int)U, (int)B, (int)nv, (int)h, (int)w, (int)N, (int)C, bpc, knn_index, gfeat, gxyz);
+  else
+    hipLaunchKernelGGL((lift_knn_gather_h16_kernel<K, T>), lift_grid(B, bpc), dim3(T), 0, s, rec, plane, pitch, points, cam, pose, feature,
+                       feature_type, (int)B, (int)nv, (int)h, (int)w, (int)N, (int)C, bpc, knn_index, gfeat, gxyz, flip, rot, points_out);
+  return mvp_launch_status();
+}
+
+int launch_lift_h16(int64_t k, const float4* rec, const uint16_t* plane, int pitch, const float* points, const float* cam, const float* pose,
+                    const void* feature, int feature_type, const int* view_slot, int64_t U, int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N,
+                    int64_t C, int64_t* knn_index, float* gfeat, float* gxyz, const uint8_t* flip, const double* rot, float* points_out,
+                    hipStream_t s) {
+  const uint16_t* f = static_cast<const uint16_t*>(feature);
+  const bool small = lift_small_workgroups(B, N, C);
+  switch (k) {
+#define MVP_CASE(KK)                                                                                                                      \
+  case KK:                                                                                                                                \
+    return small ? launch_lift_h16_t<KK, 64>(rec, plane, pitch, points, cam, pose, f, feature_type, view_slot, U, B, nv, h, w, N, C,      \
+                                             knn_index, gfeat, gxyz, flip, rot, points_out, s)                                            \
+                 : launch_lift_h16_t<KK, kLFThreads>(rec, plane, pitch, points, cam, pose, f, feature_type, view_slot, U, B, nv, h, w, N, \
+                                                     C, knn_index, gfeat, gxyz, flip, rot, points_out, s);
+    MVP_CASE(1) MVP_CASE(2) MVP_CASE(3) MVP_CASE(4) MVP_CASE(5) MVP_CASE(6) MVP_CASE(7) MVP_CASE(8)
+#undef MVP_CASE
+  }
+  return MVP_EUNSUPPORTED;
 }
 
 // K1 of every lifting entry: the search records and the depth plane of all B * nv views.
@@ -886,4 +1085,74 @@ MVP_API int mvp_lift_store_f32(const void* depth, int depth_is_u16, const float*
 #undef MVP_CASE
   }
   return MVP_EUNSUPPORTED;
+}
+
+// ---- 16-bit feature maps and stores: the three entries above reading bfloat16 / float16 rows, widened in the gather -------------------
+// Bit-equal to the `_f32` entry on the exactly widened copy; outputs unchanged (gfeature stays float32).  Forward only.
+MVP_API int mvp_lift_aug_h16(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                             const float* box, const float* points, const void* feature, int feature_type, int64_t B, int64_t nv,
+                             int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace, int64_t* knn_index,
+                             float* gfeature, float* gxyz, float* image_xyz, uint8_t* mask, const uint8_t* flip,
+                             const double* rot, float* points_out, mvp_stream_t stream) {
+  MVP_NONNULL(depth);
+  MVP_NONNULL(kinv);
+  MVP_NONNULL(cam);
+  MVP_NONNULL(pose);
+  MVP_NONNULL(points);
+  MVP_NONNULL(workspace);
+  MVP_NONNULL(knn_index);
+  if (gfeature) MVP_NONNULL(feature);
+  MVP_REQUIRE(feature_type == MVP_FEATURE_BF16 || feature_type == MVP_FEATURE_F16);
+  MVP_REQUIRE(B >= 0 && N >= 0 && nv > 0 && h > 0 && w > 0 && k >= 1 && k <= 8 && C >= 0);
+  MVP_REQUIRE(nv * (h + 8) * (w + 14) < (1ll << 31) && N < (1ll << 31) && B * (nv + 1) < 65536 && nv <= kMaxViews);
+  MVP_REQUIRE(((uintptr_t)workspace % 16) == 0 && ((uintptr_t)feature % 16) == 0 && C % 4 == 0);
+  if (gfeature) MVP_REQUIRE(C % 4 == 0 && C >= 4 && C <= 1024 && (kLFThreads % (C / 4)) == 0 && ((uintptr_t)gfeature % 16) == 0);
+  if (B == 0) return MVP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float4* rec = static_cast<float4*>(workspace);
+  uint16_t* plane = reinterpret_cast<uint16_t*>(rec + B * nv * h * w);
+  const int pitch = plane_pitch((int)w);
+  int rc = launch_lift_prepare(depth, depth_is_u16, kinv, pose, box, B, nv, h, w, pitch, rec, plane, image_xyz, mask, flip, s);
+  if (rc != MVP_OK || N == 0) return rc;
+  return launch_lift_h16(k, rec, plane, pitch, points, cam, pose, feature, feature_type, nullptr, 0, B, nv, h, w, N, C, knn_index, gfeature, gxyz,
+                         flip, rot, points_out, s);
+}
+
+MVP_API int mvp_lift_h16(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                         const float* box, const float* points, const void* feature, int feature_type, int64_t B, int64_t nv,
+                         int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace, int64_t* knn_index,
+                         float* gfeature, float* gxyz, float* image_xyz, uint8_t* mask, mvp_stream_t stream) {
+  return mvp_lift_aug_h16(depth, depth_is_u16, kinv, cam, pose, box, points, feature, feature_type, B, nv, h, w, N, C, k, workspace, knn_index,
+                          gfeature, gxyz, image_xyz, mask, nullptr, nullptr, nullptr, stream);
+}
+
+MVP_API int mvp_lift_store_h16(const void* depth, int depth_is_u16, const float* kinv, const float* cam, const float* pose,
+                               const float* box, const float* points, const void* store, int feature_type, const int32_t* view_slot,
+                               int64_t U, int64_t B, int64_t nv, int64_t h, int64_t w, int64_t N, int64_t C, int64_t k, void* workspace,
+                               int64_t* knn_index, float* gfeature, float* gxyz, mvp_stream_t stream) {
+  MVP_NONNULL(depth);
+  MVP_NONNULL(kinv);
+  MVP_NONNULL(cam);
+  MVP_NONNULL(pose);
+  MVP_NONNULL(points);
+  MVP_NONNULL(store);
+  MVP_NONNULL(view_slot);
+  MVP_NONNULL(workspace);
+  MVP_NONNULL(knn_index);
+  MVP_NONNULL(gfeature);
+  MVP_REQUIRE(feature_type == MVP_FEATURE_BF16 || feature_type == MVP_FEATURE_F16);
+  MVP_REQUIRE(B >= 0 && N >= 0 && nv > 0 && h > 0 && w > 0 && k >= 1 && k <= 8 && U >= 1);
+  MVP_REQUIRE(nv * (h + 8) * (w + 14) < (1ll << 31) && N < (1ll << 31) && B * (nv + 1) < 65536 && nv <= kMaxViews);
+  MVP_REQUIRE(((uintptr_t)workspace % 16) == 0);
+  MVP_REQUIRE(C % 4 == 0 && C >= 4 && C <= 1024 && (kLFThreads % (C / 4)) == 0 && ((uintptr_t)store % 16) == 0 && ((uintptr_t)gfeature % 16) == 0);
+  if (U >= (1ll << 31) / (h * w) + ((1ll << 31) % (h * w) != 0)) return MVP_EUNSUPPORTED;  // store rows are 32-bit: U * h * w < 2^31
+  if (B == 0) return MVP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float4* rec = static_cast<float4*>(workspace);
+  uint16_t* plane = reinterpret_cast<uint16_t*>(rec + B * nv * h * w);
+  const int pitch = plane_pitch((int)w);
+  int rc = launch_lift_prepare(depth, depth_is_u16, kinv, pose, box, B, nv, h, w, pitch, rec, plane, nullptr, nullptr, nullptr, s);
+  if (rc != MVP_OK || N == 0) return rc;
+  return launch_lift_h16(k, rec, plane, pitch, points, cam, pose, store, feature_type, view_slot, U, B, nv, h, w, N, C, knn_index, gfeature, gxyz,
+                         nullptr, nullptr, nullptr, s);
 }

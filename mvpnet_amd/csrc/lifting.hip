@@ -100,6 +100,53 @@ __global__ __launch_bounds__(kLGThreads) void lift_gather_generic_kernel(const f
   if (gxyz && c < 3) gxyz[((size_t)b * E + e) * 3 + c] = ok ? xyz[((size_t)b * P + j) * 3 + c] : 0.f;
 }
 
+// The two gathers above for 16-bit feature rows (bfloat16 / float16, picked by the launch-uniform feature_type): 8 bytes per lane (4
+// channels) widened in registers (common.h, exact), float32 rows out.  xyz stays float32.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(kLGThreads) void lift_gather_h16_kernel(const uint16_t* __restrict__ feat, int feature_type,
+                                                                     const float* __restrict__ xyz,
+                                                                     const int64_t* __restrict__ idx, int64_t P, int C,
+                                                                     int64_t E /* N*k */, float* __restrict__ gfeat,
+                                                                     float* __restrict__ gxyz) {
+  const int b = blockIdx.y;
+  const int C4 = C >> 2;
+  const int64_t t = (int64_t)blockIdx.x * kLGThreads + threadIdx.x;
+  const int64_t e = t / C4;
+  const int c4 = (int)(t - e * C4);
+  if (e >= E) return;
+  const int64_t j = idx[(size_t)b * E + e];
+  const bool ok = j >= 0 && j < P;
+  if (gfeat) {
+    u32x2 v = {0u, 0u};
+    if (ok) v = reinterpret_cast<const u32x2*>(feat + ((size_t)b * P + j) * C)[c4];
+    const bool f16 = feature_type == MVP_FEATURE_F16;
+    reinterpret_cast<float4*>(gfeat + ((size_t)b * E + e) * C)[c4] =
+        f16 ? make_float4(widen_h16_lo<true>(v.x), widen_h16_hi<true>(v.x), widen_h16_lo<true>(v.y), widen_h16_hi<true>(v.y))
+            : make_float4(widen_h16_lo<false>(v.x), widen_h16_hi<false>(v.x), widen_h16_lo<false>(v.y), widen_h16_hi<false>(v.y));
+  }
+  if (gxyz && c4 < 3) gxyz[((size_t)b * E + e) * 3 + c4] = ok ? xyz[((size_t)b * P + j) * 3 + c4] : 0.f;
+}
+
+__global__ __launch_bounds__(kLGThreads) void lift_gather_generic_h16_kernel(const uint16_t* __restrict__ feat, int feature_type,
+                                                                             const float* __restrict__ xyz,
+                                                                             const int64_t* __restrict__ idx, int64_t P, int C,
+                                                                             int64_t E, float* __restrict__ gfeat,
+                                                                             float* __restrict__ gxyz) {
+  const int b = blockIdx.y;
+  const int CC = C > 3 ? C : 3;
+  const int64_t t = (int64_t)blockIdx.x * kLGThreads + threadIdx.x;
+  const int64_t e = t / CC;
+  const int c = (int)(t - e * CC);
+  if (e >= E) return;
+  const int64_t j = idx[(size_t)b * E + e];
+  const bool ok = j >= 0 && j < P;
+  if (gfeat && c < C) {
+    const unsigned v = ok ? (unsigned)feat[((size_t)b * P + j) * C + c] : 0u;
+    gfeat[((size_t)b * E + e) * C + c] = feature_type == MVP_FEATURE_F16 ? widen_h16_lo<true>(v) : widen_h16_lo<false>(v);
+  }
+  if (gxyz && c < 3) gxyz[((size_t)b * E + e) * 3 + c] = ok ? xyz[((size_t)b * P + j) * 3 + c] : 0.f;
+}
+
 __global__ __launch_bounds__(kLGThreads) void lift_gather_bwd_kernel(const float* __restrict__ ggf,
                                                                      const int64_t* __restrict__ idx, int64_t P,
                                                                      int C, int64_t E, float* __restrict__ gfeat) {
@@ -215,6 +262,32 @@ MVP_API int mvp_lift_gather_f32(const float* feature, const float* image_xyz, co
     dim3 grid((unsigned)cdiv(E * CC, kLGThreads), (unsigned)B);
     hipLaunchKernelGGL(lift_gather_generic_kernel, grid, dim3(kLGThreads), 0, s, feature, image_xyz, index, P, (int)C,
                        E, gfeature, gxyz);
+  }
+  return mvp_launch_status();
+}
+
+// mvp_lift_gather_f32 reading bfloat16 / float16 feature rows: bit-equal to it on the exactly widened copy.  Forward only.
+MVP_API int mvp_lift_gather_h16(const void* feature, int feature_type, const float* image_xyz, const int64_t* index, int64_t B,
+                                int64_t P, int64_t C, int64_t N, int64_t k, float* gfeature, float* gxyz, mvp_stream_t stream) {
+  MVP_NONNULL(index);
+  if (gfeature) MVP_NONNULL(feature);
+  if (gxyz) MVP_NONNULL(image_xyz);
+  MVP_REQUIRE(feature_type == MVP_FEATURE_BF16 || feature_type == MVP_FEATURE_F16);
+  MVP_REQUIRE(B >= 0 && P > 0 && C >= 0 && N >= 0 && k >= 0 && B < 65536 && C < (1ll << 20));
+  MVP_REQUIRE((uintptr_t)feature % 16 == 0);
+  const int64_t E = N * k;
+  if (B == 0 || E == 0 || (!gfeature && !gxyz)) return MVP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint16_t* f = static_cast<const uint16_t*>(feature);
+  const bool vec = (C % 4 == 0) && C >= 12 && ((uintptr_t)gfeature % 16 == 0);
+  if (vec) {
+    dim3 grid((unsigned)cdiv(E * (C / 4), kLGThreads), (unsigned)B);
+    hipLaunchKernelGGL(lift_gather_h16_kernel, grid, dim3(kLGThreads), 0, s, f, feature_type, image_xyz, index, P, (int)C, E, gfeature, gxyz);
+  } else {
+    const int64_t CC = C > 3 ? C : 3;
+    dim3 grid((unsigned)cdiv(E * CC, kLGThreads), (unsigned)B);
+    hipLaunchKernelGGL(lift_gather_generic_h16_kernel, grid, dim3(kLGThreads), 0, s, f, feature_type, image_xyz, index, P, (int)C, E, gfeature,
+                       gxyz);
   }
   return mvp_launch_status();
 }

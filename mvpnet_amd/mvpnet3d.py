@@ -179,6 +179,10 @@ class MVPNet3D(nn.Module):
         else:
             feature_2d = self.net_2d({'image': images.reshape(b * nv, *images.shape[2:])})['feature']  # (B*nv,C,h,w)
         c = feature_2d.size(1)
+        # a bfloat16 / float16 map (frozen_inference(feature_dtype=...)) goes to the lift as it is: the gather widens its rows, no float32
+        # copy.  One that needs a gradient is widened here: the scatter-add backward is float32 only
+        if feature_2d.dtype in (torch.bfloat16, torch.float16) and feature_2d.requires_grad and torch.is_grad_enabled():
+            feature_2d = feature_2d.float()
         # channels-last view (B,nv,h,w,C); free when the 2D net already runs in torch.channels_last
         feature_cl = feature_2d.permute(0, 2, 3, 1).contiguous().view(b, nv, h, w, c)
         if 'knn_indices' in data_batch and 'image_xyz' in data_batch:  # loader-supplied, as in the reference

@@ -6,6 +6,17 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 
+# 16-bit feature maps and stores (the `_h16` entry points, MVP_FEATURE_* of the header): widened to float32 inside the gather, exactly
+_FEATURE_TYPES = {torch.bfloat16: L.LIMITS['MVP_FEATURE_BF16'], torch.float16: L.LIMITS['MVP_FEATURE_F16']}
+_FORWARD_ONLY = '{}: half-width (bfloat16 / float16) feature maps are forward only; pass feature.float() for a gradient'
+
+
+def _feature_args(name, feature):
+    """-> (entry point, (pointer,) or (pointer, feature_type)) for a float32 or a 16-bit feature map / store."""
+    if feature.dtype == torch.float32:
+        return name + '_f32', (L.ptr(feature),)
+    return name + '_h16', (L.ptr(feature), _FEATURE_TYPES[feature.dtype])
+
 
 def unproject(depth, kinv, pose, box=None):
     """depth (B,nv,h,w) float32 metres or int16/uint16 millimetres (raw PNG values),
@@ -67,11 +78,11 @@ class LiftGatherFunction(torch.autograd.Function):
         C = feature.size(-1)
         P = feature.numel() // (B * C)
         ctx.save_for_backward(index)
-        ctx.shape = tuple(feature.shape)
+        ctx.shape, ctx.feature_dtype = tuple(feature.shape), feature.dtype
         gfeat = torch.empty((B, N, k, C), dtype=torch.float32, device=feature.device)
         gxyz = torch.empty((B, N, k, 3), dtype=torch.float32, device=feature.device) if image_xyz is not None else None
-        L.call('mvp_lift_gather_f32', feature, L.ptr(feature), L.ptr(image_xyz), L.ptr(index), B, P, C, N, k,
-               L.ptr(gfeat), L.ptr(gxyz))
+        name, feature_args = _feature_args('mvp_lift_gather', feature)
+        L.call(name, feature, *feature_args, L.ptr(image_xyz), L.ptr(index), B, P, C, N, k, L.ptr(gfeat), L.ptr(gxyz))
         if gxyz is None:
             return gfeat
         ctx.mark_non_differentiable(gxyz)
@@ -80,6 +91,8 @@ class LiftGatherFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_gfeat, _grad_gxyz=None):
+        if ctx.feature_dtype != torch.float32:  # (lift_gather refuses such a call up front; this is for a direct apply())
+            raise RuntimeError(_FORWARD_ONLY.format('lift_gather'))
         (index,) = ctx.saved_tensors
         B, N, k = index.shape
         C = ctx.shape[-1]
@@ -93,10 +106,13 @@ class LiftGatherFunction(torch.autograd.Function):
 
 
 def lift_gather(feature, image_xyz, knn_indices):
-    """feature (B,nv,h,w,C) or (B,P,C) float32 channels-last, image_xyz (B,nv,h,w,3) or (B,P,3) or None,
-    knn_indices (B,N,k) -> gathered feature (B,N,k,C), gathered xyz (B,N,k,3) (None without image_xyz)."""
-    if feature.dtype != torch.float32 or (image_xyz is not None and image_xyz.dtype != torch.float32) or knn_indices.dtype != torch.int64:
-        raise RuntimeError('lift_gather: float32 feature/xyz and int64 indices expected')
+    """feature (B,nv,h,w,C) or (B,P,C) channels-last, float32 -- or bfloat16 / float16: widened in the gather, bit-equal to the call on
+    feature.float(), forward only --, image_xyz (B,nv,h,w,3) or (B,P,3) or None,
+    knn_indices (B,N,k) -> gathered feature (B,N,k,C) float32, gathered xyz (B,N,k,3) (None without image_xyz)."""
+    if feature.dtype in _FEATURE_TYPES and feature.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(_FORWARD_ONLY.format('lift_gather'))
+    if (feature.dtype != torch.float32 and feature.dtype not in _FEATURE_TYPES) or (image_xyz is not None and image_xyz.dtype != torch.float32) or knn_indices.dtype != torch.int64:
+        raise RuntimeError('lift_gather: float32 (or bfloat16 / float16) feature, float32 xyz and int64 indices expected')
     if image_xyz is None:
         return LiftGatherFunction.apply(feature.contiguous(), None, knn_indices.contiguous()), None
     return LiftGatherFunction.apply(feature.contiguous(), image_xyz.contiguous(), knn_indices.contiguous())
@@ -125,14 +141,16 @@ class LiftFunction(torch.autograd.Function):
         mask = torch.empty((B, nv, h, w), dtype=torch.uint8, device=depth.device) if want_image_xyz else None
         points_rot = torch.empty_like(points) if rot is not None else None
         if flip is None and rot is None:
-            L.call('mvp_lift_f32', depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points),
-                   L.ptr(feature), B, nv, h, w, N, C, k, L.ptr(ws), L.ptr(knn), L.ptr(gfeat), L.ptr(gxyz), L.ptr(xyz), L.ptr(mask))
+            name, feature_args = _feature_args('mvp_lift', feature)
+            L.call(name, depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points),
+                   *feature_args, B, nv, h, w, N, C, k, L.ptr(ws), L.ptr(knn), L.ptr(gfeat), L.ptr(gxyz), L.ptr(xyz), L.ptr(mask))
         else:
-            L.call('mvp_lift_aug_f32', depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points),
-                   L.ptr(feature), B, nv, h, w, N, C, k, L.ptr(ws), L.ptr(knn), L.ptr(gfeat), L.ptr(gxyz), L.ptr(xyz), L.ptr(mask),
+            name, feature_args = _feature_args('mvp_lift_aug', feature)
+            L.call(name, depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points),
+                   *feature_args, B, nv, h, w, N, C, k, L.ptr(ws), L.ptr(knn), L.ptr(gfeat), L.ptr(gxyz), L.ptr(xyz), L.ptr(mask),
                    L.ptr(flip), L.ptr(rot), L.ptr(points_rot))
         ctx.save_for_backward(knn)
-        ctx.shape = tuple(feature.shape)
+        ctx.shape, ctx.feature_dtype = tuple(feature.shape), feature.dtype
         outs = (gfeat, gxyz, knn)
         if want_image_xyz:
             outs += (xyz, mask)
@@ -144,6 +162,8 @@ class LiftFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_gfeat, *unused):
+        if ctx.feature_dtype != torch.float32:  # (lift refuses such a call up front; this is for a direct apply())
+            raise RuntimeError(_FORWARD_ONLY.format('lift'))
         (knn,) = ctx.saved_tensors
         B, N, k = knn.shape
         C = ctx.shape[-1]
@@ -157,15 +177,18 @@ class LiftFunction(torch.autograd.Function):
 
 
 def lift(feature, depth, kinv, cam, pose, points, k=3, box=None, return_image_xyz=False, flip=None, rot=None):
-    """feature (B,nv,h,w,C) f32 channels-last; depth (B,nv,h,w) f32 m / int16 mm; kinv, cam (B,nv,3,3);
-    pose (B,nv,4,4); points (B,N,3) -> gathered feature (B,N,k,C), gathered xyz (B,N,k,3), knn_indices (B,N,k)
+    """feature (B,nv,h,w,C) channels-last, f32 -- or bfloat16 / float16: the rows are widened inside the gather (no float32 copy of the
+    map), bit-equal to the call on feature.float(), forward only --; depth (B,nv,h,w) f32 m / int16 mm; kinv, cam (B,nv,3,3);
+    pose (B,nv,4,4); points (B,N,3) -> gathered feature (B,N,k,C) f32, gathered xyz (B,N,k,3), knn_indices (B,N,k)
     [, image_xyz (B,nv,h,w,3), image_mask (B,nv,h,w) uint8] [, rotated points (B,N,3) when `rot` is given].
     flip (B,nv) bool / uint8: views the loader mirrored (scannet_2d3d.py:293-296) -- `feature` comes from the mirrored image, the
         returned indices / image_xyz / mask are in mirrored pixel order;
     rot (B,3,3) float64: rotation applied after the search to the gathered xyz and the points (:400-409); image_xyz is returned
         un-rotated (rotate_rows does it on request)."""
-    if feature.dtype != torch.float32 or points.dtype != torch.float32 or feature.size(-1) % 4:
-        raise RuntimeError('lift: float32 channels-last feature with C % 4 == 0 expected')
+    if (feature.dtype != torch.float32 and feature.dtype not in _FEATURE_TYPES) or points.dtype != torch.float32 or feature.size(-1) % 4:
+        raise RuntimeError('lift: float32 (or bfloat16 / float16) channels-last feature with C % 4 == 0 expected')
+    if feature.dtype in _FEATURE_TYPES and feature.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(_FORWARD_ONLY.format('lift'))
     if flip is not None:
         if tuple(flip.shape) != tuple(depth.shape[:2]):
             raise RuntimeError('lift: flip must be (B, nv)')
@@ -181,12 +204,15 @@ def lift(feature, depth, kinv, cam, pose, points, k=3, box=None, return_image_xy
 
 def lift_store(store, view_slot, depth, kinv, cam, pose, points, k=3, box=None):
     """ops.lift reading the feature rows from a store shared by all chunks (mvp_lift_store_f32; scene.infer_scene_shared): no
-    (B,nv,h,w,C) tensor per batch.  store (U,h,w,C) f32 channels-last: one feature map per distinct frame; view_slot (B,nv) int32: the
+    (B,nv,h,w,C) tensor per batch.  store (U,h,w,C) channels-last, f32 or bfloat16 / float16 (mvp_lift_store_h16: widened inside the gather,
+    bit-equal to the call on store.float()): one feature map per distinct frame; view_slot (B,nv) int32: the
     store slot of view v of chunk b -- a slot outside [0,U) counts as a missing neighbour, its rows are zero --; the rest as ops.lift.
     -> gathered feature (B,N,k,C), gathered xyz (B,N,k,3), knn_indices (B,N,k) (chunk-local flat ids, as ops.lift's): bit-equal to
     ops.lift(store[view_slot.long()], ...).  Forward only: the test path, nothing here requires grad."""
-    if store.dtype != torch.float32 or points.dtype != torch.float32 or store.dim() != 4 or store.size(-1) % 4:
-        raise RuntimeError('lift_store: float32 channels-last store (U,h,w,C) with C % 4 == 0 expected')
+    if (store.dtype != torch.float32 and store.dtype not in _FEATURE_TYPES) or points.dtype != torch.float32 or store.dim() != 4 or store.size(-1) % 4:
+        raise RuntimeError('lift_store: float32 (or bfloat16 / float16) channels-last store (U,h,w,C) with C % 4 == 0 expected')
+    if store.dtype in _FEATURE_TYPES and store.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(_FORWARD_ONLY.format('lift_store'))
     if depth.dim() != 4 or tuple(store.shape[1:3]) != tuple(depth.shape[2:]):
         raise RuntimeError('lift_store: depth must be (B,nv,h,w) at the store\'s (h,w)')
     if view_slot.dtype != torch.int32 or tuple(view_slot.shape) != tuple(depth.shape[:2]):
@@ -213,7 +239,8 @@ def lift_store(store, view_slot, depth, kinv, cam, pose, points, k=3, box=None):
         knn = torch.empty((B, N, k), dtype=torch.int64, device=depth.device)
         gfeat = torch.empty((B, N, k, C), dtype=torch.float32, device=depth.device)
         gxyz = torch.empty((B, N, k, 3), dtype=torch.float32, device=depth.device)
-        L.call('mvp_lift_store_f32', depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points), L.ptr(store),
+        name, store_args = _feature_args('mvp_lift_store', store)
+        L.call(name, depth, L.ptr(depth), is_u16, L.ptr(kinv), L.ptr(cam), L.ptr(pose), L.ptr(box), L.ptr(points), *store_args,
                L.ptr(view_slot), store.size(0), B, nv, h, w, N, C, k, L.ptr(ws), L.ptr(knn), L.ptr(gfeat), L.ptr(gxyz))
     return gfeat, gxyz, knn
 

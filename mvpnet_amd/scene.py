@@ -467,25 +467,30 @@ def _frames_through(net_2d, key, images, image_normalizer, channels_last):
     return lambda frames: net_2d({'image': _test_frames(images, frames, image_normalizer, channels_last)})[key]
 
 
-def _frame_store(distinct, F, H, W, frame_batch, run, who, dev, channels=None):
+def _frame_store(distinct, F, H, W, frame_batch, run, who, dev, channels=None, dtype=None):
     """Every distinct picked frame through the 2D network once (infer_scene_shared per run, infer_scene_2d per scene).  distinct: the
     frames, an ascending host list of ints in [0, F); run(frames (b,) int64 on `dev`) -> (b,C,H,W) float32, called with at most frame_batch
     frames at a time; channels: C, or None = the first output's.  `who` refuses any other output.
-    -> (store (U,H,W,C) float32 -- channels-last memory whatever the network writes: the copy into the store makes a pixel's C values one
+    dtype: None = a float32 store of a float32 network; torch.bfloat16 / torch.float16 = a store of that type, of a network that returns
+    float32 -- the copy into the store rounds each value once, to nearest even -- or exactly that type (copied as it is).
+    -> (store (U,H,W,C) float32 or `dtype` -- channels-last memory whatever the network writes: the copy into the store makes a pixel's C values one
     contiguous row, and store.permute(0, 3, 1, 2) is the (U,C,H,W) tensor --, slot_of (F,) int32: a frame's place in the store, -1 for a
     frame that is not in it)."""
+    if dtype not in (None, torch.bfloat16, torch.float16):
+        raise RuntimeError('{}: the store is float32 (None), torch.bfloat16 or torch.float16'.format(who))
+    accepted = (torch.float32,) if dtype is None else (torch.float32, dtype)
     frames = torch.tensor(distinct, dtype=torch.int64).to(dev)
     store = None
     for lo in range(0, len(distinct), int(frame_batch)):
         part = frames[lo:lo + int(frame_batch)]
         out = run(part)
-        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float32 \
+        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype not in accepted \
                 or tuple(out.shape) != (part.numel(), out.size(1) if channels is None else channels, H, W):
-            raise RuntimeError('{}: net_2d must return a float32 (b,{},{},{}) tensor for b frames: the lifting maps\' size'.format(
-                who, 'C' if channels is None else channels, H, W))
+            raise RuntimeError('{}: net_2d must return a float32{} (b,{},{},{}) tensor for b frames: the lifting maps\' size'.format(
+                who, '' if dtype is None else ' or {}'.format(dtype), 'C' if channels is None else channels, H, W))
         if store is None:
             channels = out.size(1)
-            store = torch.empty((len(distinct), H, W, channels), dtype=torch.float32, device=dev)
+            store = torch.empty((len(distinct), H, W, channels), dtype=torch.float32 if dtype is None else dtype, device=dev)
         store[lo:lo + part.numel()].permute(0, 3, 1, 2).copy_(out)
     slot_of = torch.full((F,), -1, dtype=torch.int32, device=dev)
     slot_of[frames] = torch.arange(len(distinct), dtype=torch.int32, device=dev)
@@ -495,19 +500,23 @@ def _frame_store(distinct, F, H, W, frame_batch, run, who, dev, channels=None):
 def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                        min_nb_pts=2048, overlap=None, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None, pad_seed=0, batch_size=32,
                        max_batch_points=32 * 8192, max_bucket=32768, image_normalizer=None, channels_last=False, frame_batch=32,
-                       max_store_bytes=8 << 30):
+                       max_store_bytes=8 << 30, store_dtype=None):
     """The whole-scene test of MVPNet (mvpnet/test_mvpnet_3d.py:142-174) from a scene's raw arrays with every frame through the 2D network
     ONCE: `infer_scene(model, *prepare_scene_bucketed(...)[:3])` -- same chunks, same frames, same batches in the same order, same padded
     points, same kernels behind the lift -- without its (B,nv,3,H,W) images per batch.  Single process.
     model: an MVPNet3D; run in eval mode under no_grad, its mode is restored.  The other arguments are prepare_scene_bucketed's;
     frame_batch: frames per forward of the 2D network; max_store_bytes: the most memory a feature store may take.
+    store_dtype: None = a float32 store; torch.bfloat16 / torch.float16 = a store of that type, which holds twice the frames in the same
+    bytes and is lifted from as it is (ops.lift_store widens the rows it gathers, exactly).  With a float32 2D network this is a LOSSY
+    opt-in: every feature is rounded once, to nearest even, on its way into the store.  A network that already produces that type
+    (UNetResNet34.frozen_inference(compute_dtype, feature_dtype)) loses nothing.
 
     Neighbouring chunks pick largely the same frames, and in eval mode a frame's feature map does not depend on its batch neighbours (with
     MIOpen its last bits may depend on the batch SIZE; an elementwise network's do not).  The batches are cut into runs of consecutive
-    batches whose distinct frames fit one store (plan_store_groups, max_store_bytes // (H*W*C*4) frames; host arithmetic on the picked
+    batches whose distinct frames fit one store (plan_store_groups, max_store_bytes // (H*W*C*itemsize) frames; host arithmetic on the picked
     table -- the one device-to-host read beyond _scene_chunks' own --; the batch plan never depends on the cap).  Per run the distinct
     frames go through model.net_2d once each (raw uint8 frames through ops.prepare_frames first, as in infer_scene_2d) into one
-    channels-last float32 store (U,H,W,C); the run's batches carry `feature_store` / `view_slot` in place of `images`, so MVPNet3D lifts
+    channels-last store (U,H,W,C); the run's batches carry `feature_store` / `view_slot` in place of `images`, so MVPNet3D lifts
     with ops.lift_store -- no 2D forward, no channels-last copy per batch --, the next batch's geometry prefetched as infer_scene does; the
     store is released before the next run's is made.  A frame two runs share runs once per run.
     -> mean logits (n_pts,C), labels (n_pts,) with C where no chunk holds the point, counts (n_pts,) int32, as infer_scene.  A scene with
@@ -515,6 +524,8 @@ def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_
     dev, n_pts = points.device, points.size(0)
     if frame_batch < 1:
         raise RuntimeError('infer_scene_shared: frame_batch must be at least 1')
+    if store_dtype not in (None, torch.bfloat16, torch.float16):
+        raise RuntimeError('infer_scene_shared: store_dtype must be None (float32), torch.bfloat16 or torch.float16')
     net = _unwrap(model)
     num_classes, C = int(net.net_3d.num_classes), int(net.feat_aggreg.in_channels)
     csr = _scene_chunks(points, depth, cam_matrix, pose, overlap, num_rgbd_frames, chunk_size, chunk_stride, chunk_thresh, chunk_margin,
@@ -534,7 +545,7 @@ def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_
         sels.append(picked[lo:hi])
         frames_of_batch.append({f for row in picked_host[lo:hi] for f in row})
         lo = hi
-    runs = plan_store_groups(frames_of_batch, int(max_store_bytes) // (H * W * C * 4))
+    runs = plan_store_groups(frames_of_batch, int(max_store_bytes) // (H * W * C * (4 if store_dtype is None else 2)))
     run_of_batch = {first: r for r, (first, _, _) in enumerate(runs)}
     run_2d = _frames_through(net.net_2d, 'feature', images, image_normalizer, channels_last)
     state = {'store': None, 'slot_of': None}
@@ -543,7 +554,8 @@ def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_
         """Batch i as the model takes it; the first batch of a run makes the run's store (the previous one is released first)."""
         if i in run_of_batch:
             state['store'] = state['slot_of'] = None
-            state['store'], state['slot_of'] = _frame_store(runs[run_of_batch[i]][2], F, H, W, frame_batch, run_2d, 'infer_scene_shared', dev, C)
+            state['store'], state['slot_of'] = _frame_store(runs[run_of_batch[i]][2], F, H, W, frame_batch, run_2d, 'infer_scene_shared', dev, C,
+                                                            store_dtype)
         return dict(batch, feature_store=state['store'], view_slot=state['slot_of'][sels[i]].contiguous())
 
     try:

@@ -112,6 +112,7 @@ class UNetResNet34(nn.Module):
         """Undo frozen_inference(): drop the folded runtime copy, parameters trainable again, train() works normally."""
         self.__dict__.pop('_fast', None)
         self.__dict__.pop('_fast_dtype', None)
+        self.__dict__.pop('_feature_dtype', None)
         self.__dict__['_frozen'] = False  # the load_state_dict hook stays registered but no longer re-creates the folded copy
         for p in self.parameters():
             p.requires_grad_(True)
@@ -125,7 +126,10 @@ class UNetResNet34(nn.Module):
                 return fast(data_dict)
             with torch.autocast(device_type=data_dict['image'].device.type, dtype=dtype):
                 out = fast(data_dict)
-            return {k: v.float() for k, v in out.items()}  # the lifting kernels take fp32 feature rows
+            # absent = float32 features (whoever sets `_fast_dtype` alone keeps getting them); else the 16-bit map goes out as computed,
+            # channels-last: ops.lift widens its rows inside the gather.  The logits are float32 either way
+            keep = self.__dict__.get('_feature_dtype')
+            return {k: v if (k == 'feature' and v.dtype == keep) else v.float() for k, v in out.items()}
         x = data_dict['image']
         h, w = x.shape[2], x.shape[3]
         pad_h, pad_w = (h + 15) // 16 * 16 - h, (w + 15) // 16 * 16 - w  # zero-pad to multiples of 16 (:66-73)
@@ -157,19 +161,28 @@ class UNetResNet34(nn.Module):
 
     # ------------------------------------------------------------------ frozen, folded, channels-last
     @torch.no_grad()
-    def frozen_inference(self, compute_dtype=None):
+    def frozen_inference(self, compute_dtype=None, feature_dtype=None):
         """compute_dtype (e.g. torch.bfloat16; default None = fp32, the reference's arithmetic): run the frozen convolutions under
         autocast in that type -- an opt-in speed / accuracy trade for the 2D branch only (bench field with_2d_network: 27.4 -> 17.6 ms
-        per step at B = 32); the features handed to the lifting kernels stay fp32 tensors.
+        per step at B = 32); the features handed to the lifting kernels stay fp32 tensors unless feature_dtype says otherwise.
+        feature_dtype (default None = every output `.float()`, as before): equal to a 16-bit compute_dtype, 'feature' is returned in that
+        type as the last convolution wrote it, channels-last, without the widened copy -- the same values: the lift (ops.lift, MVPNet3D)
+        widens the rows it gathers, exactly; forward only.  'seg_logit' stays float32.  Any other combination raises ValueError.
         Eval mode, requires_grad off, and a FOLDED RUNTIME COPY of the network (every BatchNorm folded into its convolution,
         torch.channels_last) that eval-mode forward() dispatches to.  The module itself keeps the reference's parameter layout:
         `state_dict()` still has the 426 reference keys, a full MVPNet3D checkpoint written by the reference loads, one saved
         here loads there; the copy is rebuilt after every `load_state_dict` and follows `.to()` / `.cuda()`.  Use on the
         frozen 2D branch of MVPNet (train_mvpnet_3d.py freezes net_2d)."""
+        if feature_dtype is not None and (feature_dtype != compute_dtype or feature_dtype not in (torch.bfloat16, torch.float16)):
+            raise ValueError('frozen_inference: feature_dtype must be None or equal to a bfloat16 / float16 compute_dtype')
         self.eval()
         for p in self.parameters():
             p.requires_grad_(False)
         self.__dict__['_fast_dtype'] = compute_dtype
+        if feature_dtype is None:
+            self.__dict__.pop('_feature_dtype', None)
+        else:
+            self.__dict__['_feature_dtype'] = feature_dtype
         self.__dict__['_frozen'] = True
         self._refold()
         if not self.__dict__.get('_refold_hooked'):
@@ -186,6 +199,7 @@ class UNetResNet34(nn.Module):
         fast.__dict__.pop('_refold_hooked', None)
         fast.__dict__.pop('_frozen', None)
         fast.__dict__.pop('_fast_dtype', None)
+        fast.__dict__.pop('_feature_dtype', None)
         fast._load_state_dict_post_hooks.clear()
         fast._fold_in_place()
         self.__dict__['_fast'] = fast  # NOT a registered sub-module: invisible to state_dict() / parameters()
