@@ -254,6 +254,23 @@ int mvp_lift_gather_f32(const float* feature, const float* image_xyz, const int6
                         int64_t C, int64_t N, int64_t k, float* gfeature, float* gxyz, mvp_stream_t stream);
 int mvp_lift_gather_backward_f32(const float* grad_gfeature, const int64_t* index, int64_t B, int64_t P, int64_t C,
                                  int64_t N, int64_t k, float* grad_feature, mvp_stream_t stream);
+/* The same gradient as a GATHER: reproducible, no zero fill, no float atomics (csrc/lift_bwd.hip).  With E = N*k and e = n*k + slot:
+ *   grad_feature[b,j,:] is an accumulator that starts at +0.0f and adds grad_gfeature[b,e,:] for every e with index[b,e] == j, in
+ *   ASCENDING e, by plain float32 additions (one rounding each) -- the sequential loop over the chunk's edges.  The result is a function
+ *   of the inputs alone; mvp_lift_gather_backward_f32 adds the same terms in the order its atomics arrive.
+ *   grad_gfeature (B,N,k,C), index (B,N,k) int64 as the mvp_lift_* entries write it (flat pixel ids, mirrored ids for flipped views, -1
+ *   for a missing neighbour): an index outside [0,P) is ignored, never an address.
+ *   -> grad_feature (B,P,C): EVERY element is written (the caller does not pre-fill; a pixel nobody names gets +0.0f).
+ *   workspace: caller-owned device scratch of mvp_lift_backward_workspace_bytes(B,P,N,k) bytes, 16-byte aligned (else MVP_EINVAL),
+ *   reusable once the launches have run (stream order): the transposed index, offsets (B,P+1) and slots (B,E) int32, built by the first
+ *   launch with integer LDS atomics on counters only (every list is then sorted); the second launch walks the lists and stores the rows.
+ *   C % 4 == 0 with 16-byte aligned grad_gfeature / grad_feature: 16 bytes per lane (C = 20, MVPNet2D's logits, included); any other C:
+ *   one element per lane.  E == 0 still writes the zero map; C == 0 or B == 0 does nothing.
+ *   Positions and pixels are 32-bit inside: E >= 2^31, P >= 2^31 or B >= 65536 is MVP_EUNSUPPORTED (the workspace size is then 0, as
+ *   for a negative argument).  All checks come before the first launch. */
+int64_t mvp_lift_backward_workspace_bytes(int64_t B, int64_t P, int64_t N, int64_t k);
+int mvp_lift_backward_f32(const float* grad_gfeature, const int64_t* index, int64_t B, int64_t P, int64_t C,
+                          int64_t N, int64_t k, void* workspace, float* grad_feature, mvp_stream_t stream);
 
 /* fused lifting: un-projection + exact pixel k-NN + channels-last gather in two launches
  * (replaces scannet_2d3d.py:254-313 + mvpnet_3d.py:99-109 end to end).

@@ -238,9 +238,11 @@ def _fn(name):
 
 
 # REPRODUCIBLE MODE (MVP_DETERMINISTIC=1 / set_deterministic(True)): the weight-gradient kernels flush their workgroups' partial tiles
-# through a workspace and an ordered reduction (mvp_mlp_weight_grad_ws_f32, mvp_mlp_layer_backward_ws_f32) instead of fp32 atomics -- the
-# last float32 atomics of a training step; with it every parameter after a step is the same bit for bit in every run
-# (tests/test_determinism_gpu.py).  Costs ~2 % of the step (the reductions are extra launches, five of them on the critical stream):
+# through a workspace and an ordered reduction (mvp_mlp_weight_grad_ws_f32, mvp_mlp_layer_backward_ws_f32) instead of fp32 atomics, and the
+# gradient of the lift into a trainable 2D feature map is a gather over a transposed pixel index (ops.lift_gather_backward =
+# mvp_lift_backward_f32) instead of a memset + fp32 atomics -- with the two, no float32 atomic is left in our kernels and every parameter
+# after a step is the same bit for bit in every run (tests/test_determinism_gpu.py, tests/test_lift_backward_gpu.py).  With a trainable
+# 2D branch that covers OUR kernels: the determinism of MIOpen's convolution backward inside the 2D network is not ours to promise.  Costs ~2 % of the step (the reductions are extra launches, five of them on the critical stream):
 # 8.20 -> 8.39 ms, so it is off by default; the atomics' run-to-run noise is ~1e-7 relative per gradient element.  One workspace per
 # (device, stream) -- a kernel and its reduction run in order on that stream --, handed out here to every caller of the two entry points.
 DW_WORKSPACE = os.environ.get('MVP_DETERMINISTIC', '0') == '1'

@@ -6,7 +6,7 @@ from .ball_query import ball_query, ball_query_distance
 from .group_points import group_points
 from .knn_distance import knn_distance
 from .interpolate import feature_interpolate
-from .lifting import unproject, pixel_knn, lift_gather, lift, lift_store, rotate_rows
+from .lifting import unproject, pixel_knn, lift_gather, lift_gather_backward, lift, lift_store, rotate_rows
 from .overlap import rgbd_overlap, select_frames_batched, pack_bits, unpack_bits
 from .vote import vote_nearest, lift_vote, vote_finish
 from .sample import sample_chunks
@@ -18,7 +18,7 @@ from .resize import resize_frames, prepare_labels
 from .frame_eval import frame_confusion, label_histogram
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
-           'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift', 'lift_store', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
+           'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift_gather_backward', 'lift', 'lift_store', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
            'pack_bits', 'unpack_bits', 'vote_nearest', 'lift_vote', 'vote_finish', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
            'pack_cloud', 'ensemble_softmax', 'label_confusion',
            'prepare_frames', 'resize_frames', 'prepare_labels', 'frame_confusion', 'label_histogram']

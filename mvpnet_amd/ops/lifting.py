@@ -67,6 +67,47 @@ def pixel_knn(image_xyz, image_mask, points, k, cam=None, pose=None, return_dist
     return (index, dist) if return_distance else index
 
 
+def lift_gather_backward(grad_gfeat, knn_indices, P):
+    """Gradient of the lift with respect to the feature map, as a gather (mvp_lift_backward_f32: a transposed index, then one store per
+    map row): grad_gfeat (B,N,k,C) float32, knn_indices (B,N,k) int64 as ops.lift / ops.pixel_knn return them, P pixels per chunk
+    -> (B,P,C) float32 with out[b,j] = the sum of grad_gfeat[b,n,s] over the (n,s) with knn_indices[b,n,s] == j, added in ascending
+    n*k + s from +0.0 -- the same bits in every run, no float atomics.  Indices outside [0,P) (-1: a missing neighbour) are ignored."""
+    if grad_gfeat.dtype != torch.float32 or knn_indices.dtype != torch.int64:
+        raise RuntimeError('lift_gather_backward: float32 gradient and int64 indices expected')
+    if knn_indices.dim() != 3 or grad_gfeat.dim() != 4 or tuple(grad_gfeat.shape[:3]) != tuple(knn_indices.shape):
+        raise RuntimeError('lift_gather_backward: grad_gfeat (B,N,k,C) and knn_indices (B,N,k) expected')
+    P = int(P)
+    if P <= 0:
+        raise RuntimeError('lift_gather_backward: P > 0 expected')
+    L.require_gpu(grad_gfeat, knn_indices)
+    B, N, k, C = grad_gfeat.shape
+    out = torch.empty((B, P, C), dtype=torch.float32, device=grad_gfeat.device)
+    if B == 0 or C == 0:
+        return out
+    nbytes = L.lib().mvp_lift_backward_workspace_bytes(B, P, N, k)
+    if nbytes <= 0:
+        raise RuntimeError('lift_gather_backward: shape beyond the 32-bit positions of the kernels (N*k, P < 2^31, B < 65536)')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_gfeat.device)
+    L.call('mvp_lift_backward_f32', grad_gfeat, L.ptr(grad_gfeat), L.ptr(knn_indices), B, P, C, N, k, L.ptr(ws), L.ptr(out))
+    return out
+
+
+# Which entry the backward of lift / lift_gather takes outside the reproducible mode.  The reproducible mode (_lib.DW_WORKSPACE) always
+# takes the gather; DESIGN.md 4 "Lift backward" holds the measurement this default follows (tools/bench_lift_backward.py).
+GATHER_BACKWARD_BY_DEFAULT = False
+
+
+def _lift_backward(grad_gfeat, index, shape, P):
+    g = grad_gfeat.contiguous()
+    B, N, k = index.shape
+    C = shape[-1]
+    if L.DW_WORKSPACE or GATHER_BACKWARD_BY_DEFAULT:
+        return lift_gather_backward(g, index, P).view(shape)
+    grad = torch.empty(shape, dtype=torch.float32, device=g.device)
+    L.call('mvp_lift_gather_backward_f32', g, L.ptr(g), L.ptr(index), B, P, C, N, k, L.ptr(grad))
+    return grad
+
+
 class LiftGatherFunction(torch.autograd.Function):
     """Channels-last replacement of the two group_points calls in MVPNet3D.forward
     (mvpnet/models/mvpnet_3d.py:103,109); gradient flows to the feature map only."""
@@ -94,15 +135,10 @@ class LiftGatherFunction(torch.autograd.Function):
         if ctx.feature_dtype != torch.float32:  # (lift_gather refuses such a call up front; this is for a direct apply())
             raise RuntimeError(_FORWARD_ONLY.format('lift_gather'))
         (index,) = ctx.saved_tensors
-        B, N, k = index.shape
-        C = ctx.shape[-1]
         P = 1
         for s in ctx.shape[1:-1]:
             P *= s
-        grad = torch.empty(ctx.shape, dtype=torch.float32, device=grad_gfeat.device)
-        g = grad_gfeat.contiguous()
-        L.call('mvp_lift_gather_backward_f32', g, L.ptr(g), L.ptr(index), B, P, C, N, k, L.ptr(grad))
-        return grad, None, None
+        return _lift_backward(grad_gfeat, index, ctx.shape, P), None, None
 
 
 def lift_gather(feature, image_xyz, knn_indices):
@@ -165,15 +201,10 @@ class LiftFunction(torch.autograd.Function):
         if ctx.feature_dtype != torch.float32:  # (lift refuses such a call up front; this is for a direct apply())
             raise RuntimeError(_FORWARD_ONLY.format('lift'))
         (knn,) = ctx.saved_tensors
-        B, N, k = knn.shape
-        C = ctx.shape[-1]
         P = 1
         for s in ctx.shape[1:-1]:
             P *= s
-        grad = torch.empty(ctx.shape, dtype=torch.float32, device=grad_gfeat.device)
-        g = grad_gfeat.contiguous()
-        L.call('mvp_lift_gather_backward_f32', g, L.ptr(g), L.ptr(knn), B, P, C, N, k, L.ptr(grad))
-        return (grad,) + (None,) * 10
+        return (_lift_backward(grad_gfeat, knn, ctx.shape, P),) + (None,) * 10
 
 
 def lift(feature, depth, kinv, cam, pose, points, k=3, box=None, return_image_xyz=False, flip=None, rot=None):
