@@ -379,6 +379,56 @@ int mvp_select_frames_ranges_u32(const uint32_t* overlap_bits, const uint32_t* c
                                  const int64_t* frame_count, int64_t Ftot, int64_t C, int64_t W, int64_t n_pick, int64_t* picked,
                                  int32_t* gain, mvp_stream_t stream);
 
+/* ---- scene cloud from RGB-D frames (NEW on the device; csrc/fuse_cloud.hip) ----
+ * Replaces the one input the whole-scene calls could not make: the reference reads `points` from the vertices of ScanNet's offline mesh
+ * reconstruction (mvpnet/data/preprocess/preprocess.py:204, the PLY of the scan).  Here the cloud is a voxel-grid fusion of the
+ * un-projected depth pixels, in integers, so the result does not depend on the order in which frames or pixels arrive.
+ *   depth (F,h,w) metres float32 or millimetres uint16; kinv (F,3,3), pose (F,4,4) float32; images (F,h,w,3) uint8 or NULL
+ * Pinned definition, per pixel (f, v, u):
+ *   - X = the float32 world point mvp_unproject_* writes for it with box = NULL (float64 math, rounded once);
+ *   - valid iff z_cam > 0 (that mask), the three coordinates are finite with |coordinate| < 32768, depth_min <= d <= depth_max on the
+ *     float32 depth in metres (pass -INFINITY / INFINITY for no bound; a NaN depth is never valid), and every voxel index
+ *     i_a = floor((double)X_a / voxel) -- a float64 DIVISION -- lies in [-2^20, 2^20).  Invalid pixels are ignored;
+ *   - key = ((i_z + 2^20) << 42) | ((i_y + 2^20) << 21) | (i_x + 2^20), unsigned 64-bit; all ones = the empty mark (no valid key);
+ *   - the voxel's count += 1, sum_a += llrint((double)X_a * 65536) (int64, nearest even), and with images csum_c += channel (uint64).
+ * The table is caller memory of mvp_fuse_cloud_table_bytes(capacity, colors) bytes, 8-byte aligned, `capacity` a power of two:
+ *     uint64 key[capacity] | int64 sum[capacity][3] | uint64 csum[capacity][3] (only with colors != 0) | uint32 count[capacity] |
+ *     uint32 overflow[2]                                                      (the size rounded up to a multiple of 8)
+ * The caller fills key[] with all ones and everything behind it with zero before the first insert; any number of inserts may follow.
+ * Open addressing, linear probing from a mix of the key: a 64-bit compare-and-swap claims or finds the slot (old == empty or old == key:
+ * this slot; otherwise the next one), then integer atomic adds.  The probe loop is bounded by `capacity` steps and never waits for
+ * another lane.  A pixel that finds neither its key nor an empty slot sets overflow[0] = 1 and is dropped: nothing outside the table is
+ * written.  No allocation, no synchronisation.
+ *
+ * mvp_fuse_cloud_table_bytes: the table's size; 0 unless capacity is a power of two in [1, 2^31).
+ * mvp_fuse_cloud_insert_*: MVP_ENULL (depth, kinv, pose, table); MVP_EINVAL for F < 0, h or w < 1, voxel not finite or <= 0, a NaN
+ *   bound, capacity < 1 or not a power of two, images given with colors == 0; MVP_EUNSUPPORTED for F*h*w >= 2^31 or capacity >= 2^31.
+ *   F == 0: nothing is launched.
+ * mvp_fuse_cloud_finish: slots (n,) int64 = the table slots that survive, in ascending key order (the caller's compaction and sort;
+ *   a slot outside [0, capacity) is skipped); one lane per output row r:
+ *     points[r,a] = (float)((double)sum_a / (double)count * 2^-16);  colors[r,c] = (2 * csum_c + count) / (2 * count) as uint8
+ *     counts[r] = count as int32;  rank_of_slot[slots[r]] = r   (rank_of_slot (capacity,) int32, filled with -1 by the caller)
+ *   MVP_ENULL (table, slots, points, counts, rank_of_slot); MVP_EINVAL for n < 0, n > capacity, a bad capacity, colors_out given with
+ *   colors == 0; MVP_EUNSUPPORTED for capacity >= 2^31.  n == 0: nothing is launched.
+ * mvp_fuse_cloud_lookup_*: pixel_point (F,h,w) int32 = rank_of_slot[slot of the pixel's key], -1 for an invalid pixel (same rule, same
+ *   bounds) and for a key the table does not hold; the probe only reads.  Any frames, fused ones or others.  Errors as for insert, and
+ *   MVP_ENULL for rank_of_slot or pixel_point. */
+size_t mvp_fuse_cloud_table_bytes(int64_t capacity, int colors);
+int mvp_fuse_cloud_insert_f32(const float* depth_m, const float* kinv, const float* pose, const uint8_t* images, int64_t F, int64_t h,
+                              int64_t w, double voxel, float depth_min, float depth_max, void* table, int64_t capacity, int colors,
+                              mvp_stream_t stream);
+int mvp_fuse_cloud_insert_u16(const uint16_t* depth_mm, const float* kinv, const float* pose, const uint8_t* images, int64_t F, int64_t h,
+                              int64_t w, double voxel, float depth_min, float depth_max, void* table, int64_t capacity, int colors,
+                              mvp_stream_t stream);
+int mvp_fuse_cloud_finish(const void* table, int64_t capacity, int colors, const int64_t* slots, int64_t n, float* points,
+                          uint8_t* colors_out, int32_t* counts, int32_t* rank_of_slot, mvp_stream_t stream);
+int mvp_fuse_cloud_lookup_f32(const float* depth_m, const float* kinv, const float* pose, int64_t F, int64_t h, int64_t w, double voxel,
+                              float depth_min, float depth_max, const void* table, int64_t capacity, const int32_t* rank_of_slot,
+                              int32_t* pixel_point, mvp_stream_t stream);
+int mvp_fuse_cloud_lookup_u16(const uint16_t* depth_mm, const float* kinv, const float* pose, int64_t F, int64_t h, int64_t w,
+                              double voxel, float depth_min, float depth_max, const void* table, int64_t capacity,
+                              const int32_t* rank_of_slot, int32_t* pixel_point, mvp_stream_t stream);
+
 /* ---- training chunks (NEW on the device; the reference draws them in a data-loader worker) ----
  * One call draws B training chunks from resident scenes: ScanNet2D3DChunks.__getitem__ (mvpnet/data/scannet_2d3d.py:341-381) and the
  * base-point mask of get_rgbd_data (:199-204), without a host synchronisation and without an allocation (graph-capturable).

@@ -16,12 +16,13 @@ from .ensemble import ensemble_softmax, label_confusion
 from .frames import prepare_frames
 from .resize import resize_frames, prepare_labels
 from .frame_eval import frame_confusion, label_histogram
+from .fuse_cloud import CloudFuser, fuse_cloud
 
 __all__ = ['farthest_point_sample', 'ball_query', 'ball_query_distance', 'group_points', 'knn_distance',
            'feature_interpolate', 'unproject', 'pixel_knn', 'lift_gather', 'lift_gather_backward', 'lift', 'lift_store', 'rotate_rows', 'rgbd_overlap', 'select_frames_batched',
            'pack_bits', 'unpack_bits', 'vote_nearest', 'lift_vote', 'vote_finish', 'sample_chunks', 'sample_scenes', 'gather_cloud', 'scene_chunks', 'pack_chunks',
            'pack_cloud', 'ensemble_softmax', 'label_confusion',
-           'prepare_frames', 'resize_frames', 'prepare_labels', 'frame_confusion', 'label_histogram']
+           'prepare_frames', 'resize_frames', 'prepare_labels', 'frame_confusion', 'label_histogram', 'CloudFuser', 'fuse_cloud']
 
 
 def as_point_major(x, transpose):

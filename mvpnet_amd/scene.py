@@ -567,6 +567,43 @@ def infer_scene_shared(model, points, depth, cam_matrix, pose, images, *, chunk_
     return _vote_chunk_logits(outs, [chunk_inds[c] for c in order], n_pts, len(order), num_classes)
 
 
+def scene_from_rgbd(depth, cam_matrix, pose, images=None, *, voxel=0.05, min_samples=1, max_voxels=None, depth_min=None, depth_max=None):
+    """The `points` every whole-scene call takes, made from the recording itself (new: the reference reads the vertices of ScanNet's offline
+    mesh, mvpnet/data/preprocess/preprocess.py:204): the voxel-grid fusion of the un-projected depth pixels, ops.fuse_cloud.
+    depth (F,h,w) float32 metres or (u)int16 millimetres on the device; cam_matrix (3,3) / (4,4) intrinsics OF THE DEPTH MAPS' RESOLUTION,
+    array or tensor, (F,3,3) for per-frame intrinsics, inverted as chunks.compute_rgbd_overlap does; pose (F,4,4) float32; images
+    (F,h,w,3) uint8 colour frames of the depth maps' size, or None; voxel: metres; min_samples: pixels a voxel needs to become a point;
+    max_voxels: None = the pixel count; depth_min / depth_max: metres, pixels outside are ignored.
+    -> {'points' (n,3) float32, 'colors' (n,3) uint8 or None, 'count' (n,) int32, 'pixel_point' (F,h,w) int32: each pixel's point, -1 where
+    it has none}.  Exact and independent of the frames' order.  A fused cloud is denser where frames overlap and sparser far from the
+    camera than a mesh's vertices; what that does to weights trained on mesh vertices has not been measured."""
+    import numpy as np
+    if not torch.is_tensor(depth):
+        raise RuntimeError('scene_from_rgbd: depth must be a (F,h,w) tensor')
+    kinv = torch.from_numpy(np.ascontiguousarray(CH._kinv_of(cam_matrix))).to(depth.device)
+    pose = pose.contiguous() if torch.is_tensor(pose) else pose
+    points, colors, count, pixel_point = ops.fuse_cloud(depth.contiguous(), kinv, pose, None if images is None else images.contiguous(), voxel=voxel,
+                                                        max_voxels=max_voxels, min_samples=min_samples, depth_min=depth_min, depth_max=depth_max)
+    return {'points': points, 'colors': colors, 'count': count, 'pixel_point': pixel_point}
+
+
+def infer_rgbd(model, depth, cam_matrix, pose, images, *, voxel, min_samples=1, max_voxels=None, depth_min=None, depth_max=None, **scene_kwargs):
+    """An RGB-D recording labelled from its own frames: scene_from_rgbd, then infer_scene_shared on the fused points with the same frames.
+    model, depth, cam_matrix, pose, images and scene_kwargs are infer_scene_shared's (chunk_size, chunk_stride, ..., lift_depth,
+    image_normalizer, ...); voxel, min_samples, max_voxels, depth_min, depth_max are scene_from_rgbd's.  The cloud takes its colours from
+    `images` when they are raw (F,h,w,3) uint8 frames of the depth maps' size, and has none otherwise.
+    -> scene_from_rgbd's dict + 'mean' (n,C), 'label' (n,) int64, 'vote_count' (n,) int32 -- infer_scene_shared's three -- and
+    'label_frames' (F,h,w) int64: the points' labels read back through pixel_point, C ("no prediction") where pixel_point is -1."""
+    raw = torch.is_tensor(images) and images.dtype == torch.uint8 and images.dim() == 4 and tuple(images.shape[:3]) == tuple(depth.shape)
+    cloud = scene_from_rgbd(depth, cam_matrix, pose, images if raw else None, voxel=voxel, min_samples=min_samples, max_voxels=max_voxels,
+                            depth_min=depth_min, depth_max=depth_max)
+    mean, label, votes = infer_scene_shared(model, cloud['points'], depth, cam_matrix, pose, images, **scene_kwargs)
+    num_classes = mean.size(1)
+    pp = cloud['pixel_point'].long()
+    label_frames = torch.where(pp >= 0, label[pp.clamp(min=0)] if label.numel() else pp, torch.full((), num_classes, dtype=torch.int64, device=pp.device))
+    return dict(cloud, mean=mean, label=label, vote_count=votes, label_frames=label_frames)
+
+
 def infer_scene_2d(model, points, depth, cam_matrix, pose, images, *, chunk_size, chunk_stride, chunk_thresh, chunk_margin, num_rgbd_frames, k,
                    overlap=None, lift_depth=None, num_base_pts=2000, radius=0.1, generator=None, image_normalizer=None, channels_last=False,
                    frame_batch=32):
